@@ -8,6 +8,10 @@ host.  Inputs are synthetic and already resident in HBM (SURVEY.md §8d protocol
 tensors of the real architecture (no checkpoints/network in this environment).
 
   python bench.py --gpus N --steps K --warmup W          (N>1: launched by torch.distributed.run, one rank per GPU)
+  python bench.py ... --full                             (every other leg too: on_policy, latency by exit, roofline, batched, CPU ...)
+  python bench.py ... --dump-outputs DIR                 (what the last timed step returned, as DIR/<field>.npy)
+
+A plain run sets up, warms up, times K steps and prints the headline line; --full adds the legs beside it.
 
 Each rank owns a full model replica + its own environment stream (the path shards by environment):
 no data-path collective; RCCL is used only for the barrier and the final metric reduction -> "scaling": "weak".
@@ -79,6 +83,13 @@ def parse():
     ap.add_argument("--full-depth-only", type=int, default=0, metavar="K",
                     help="profiling aid: run K eager full-depth control steps (every kernel executes, no exit skipping) and "
                          "leave - the workload of the rocprofv3 --pmc passes (tools/profile_bench.sh)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline: threshold calibration + on_policy (one environment), latency by exit, "
+                         "scripted, surface, roofline, the env-batched legs and the CPU baseline.  Without it a run sets up, warms up, "
+                         "times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller (one array per result field, float32 / float64, a "
+                         "leading axis of environments) as DIR/<name>.npy")
     return ap.parse_args()
 
 
@@ -608,24 +619,29 @@ def run_workload(args, cfg, sd_dev, B, rank, world, local_rank, dist, max_layer,
     # thresholds for the target distribution p_k ~ exit_ratio^k.  The committed oracle traces (tests/golden/episode_full.npz)
     # are made the same way.  In shadow mode the state commits at the first exit whose criterion fires: thresholds
     # [-1]*k + [1e8] make that exit k.
+    # One environment: the headline runs on scripted verdicts and needs no thresholds, so calibration (with `on_policy`) is a --full leg;
+    # env batches: the headline IS the on-policy leg.
     real = ctl.real_num_exit
-    gen = torch.Generator().manual_seed(4242)
-    vals = []
-    eng.reset()
-    eng.cur_step = 0
-    for i in range(args.calib_steps):
-        k = int(torch.randint(0, real, (1,), generator=gen))
-        eng.set_thresholds([-1.0] * k + [1e8] * (real - k))
-        rgb, grip = frames[i % POOL]
-        r = eng.step(rgb, grip, ids, None, shadow=True)
-        for re in (r if B > 1 else [r]):
-            vals.append(re["deltas"][:real].clone())
-    values = torch.stack(vals, dim=1)                      # (n_exit, n_samples)
-    ctl.set_threshold_from_values(values, args.exit_ratio, cfg.llm_name)
-    thr = ctl.threshold_list()
-    eng.set_thresholds(thr)
+    thr = None
+    if args.full or B > 1:
+        gen = torch.Generator().manual_seed(4242)
+        vals = []
+        eng.reset()
+        eng.cur_step = 0
+        for i in range(args.calib_steps):
+            k = int(torch.randint(0, real, (1,), generator=gen))
+            eng.set_thresholds([-1.0] * k + [1e8] * (real - k))
+            rgb, grip = frames[i % POOL]
+            r = eng.step(rgb, grip, ids, None, shadow=True)
+            for re in (r if B > 1 else [r]):
+                vals.append(re["deltas"][:real].clone())
+        values = torch.stack(vals, dim=1)                      # (n_exit, n_samples)
+        ctl.set_threshold_from_values(values, args.exit_ratio, cfg.llm_name)
+        thr = ctl.threshold_list()
+        eng.set_thresholds(thr)
 
     real_n = ctl.real_num_exit
+    last = []                                              # what the last timed step returned (--dump-outputs)
 
     def timed(n_steps, pre, slots=None):
         """`pre` untimed + `n_steps` timed control steps (contract: barrier + synchronize on both sides); slots: scripted verdicts
@@ -651,6 +667,7 @@ def run_workload(args, cfg, sd_dev, B, rank, world, local_rank, dist, max_layer,
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         exit_sum, hist = 0, [0] * cfg.n_layers
+        r = None
         for i in range(pre, pre + n_steps):
             r = one(i)
             for re in (r if B > 1 else [r]):
@@ -660,14 +677,16 @@ def run_workload(args, cfg, sd_dev, B, rank, world, local_rank, dist, max_layer,
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
-        return time.perf_counter() - t0, exit_sum, hist
+        dt = time.perf_counter() - t0
+        last[:] = [] if r is None else (r if B > 1 else [r])
+        return dt, exit_sum, hist
 
     # ---- on-policy leg (secondary): the REAL criterion with the calibrated thresholds, mid-episode (burn-in first: 20 steps right after
     # a reset averaged exit layer 9.8, 300 steps 4.45 in round 1).  Its depth is whatever the synthetic episode's own deltas give - with
     # random weights they are not the calibration deltas - which is why it is not the headline (318 <-> 357 <-> 387
     # steps/s between runs of the same code with the 4th digit of a threshold).
     on_policy = None
-    n_on = args.on_policy_steps if B == 1 else timed_steps
+    n_on = (args.on_policy_steps if args.full else 0) if B == 1 else timed_steps
     if n_on > 0:
         dt, xs, hist = timed(n_on, args.burn_in + warmup)
         on_policy = {"value": round(world * n_on * B / dt, 2), "unit": "action-steps/s", "steps": n_on, "avg_exit_layer": round(xs / (n_on * B), 3),
@@ -696,10 +715,15 @@ def run_workload(args, cfg, sd_dev, B, rank, world, local_rank, dist, max_layer,
         # device-side verdict, host-fed graph pieces) with the verdicts scripted to the calibration target mix, stratified - the depth
         # of the timed window is the target's whatever --steps is
         slots = target_schedule(real_n, args.exit_ratio, timed_steps, seed=99)
+        if n_on == 0:
+            # set-up in place of the on-policy leg (--full): as many untimed steps of this schedule capture the graph pieces and start
+            # the timed window on a GPU and host as warm as after that leg
+            timed(args.burn_in + args.on_policy_steps, warmup, slots)
         eng.reset()
         eng.cur_step = 0
         elapsed, exit_sum, hist = timed(timed_steps, warmup, slots)
-        eng.set_thresholds(thr)
+        if thr is not None:
+            eng.set_thresholds(thr)
         n_timed = timed_steps
 
     stats = torch.tensor([elapsed, float(exit_sum), float(n_timed * B)], dtype=torch.float64,
@@ -718,7 +742,24 @@ def run_workload(args, cfg, sd_dev, B, rank, world, local_rank, dist, max_layer,
                      "slowest_over_fastest_time": round(float(tmax[0]) / max(float(tmin[0]), 1e-12), 4)}
     t_max, exits, n_steps = float(stats[0]), float(stats[1]), float(stats[2])
     return dict(eng=eng, ctl=ctl, frames=frames, ids=ids, T=T, t_max=t_max, value=n_steps / t_max, avg_exit=exits / n_steps, thr=thr,
-                hist=hist, setup_s=setup_s, on_policy=on_policy, n_timed=n_timed, rank_rate=rank_rate)
+                hist=hist, setup_s=setup_s, on_policy=on_policy, n_timed=n_timed, rank_rate=rank_rate, last=last)
+
+
+def dump_outputs(results, out_dir):
+    """What the last timed step handed its caller (``DeerEngine.step``: one dict per environment) as out_dir/<field>.npy, environments
+    along the first axis: tensors as float32, integer fields as float64.  `deltas` of the exit checks that did not run (NaN in the
+    result) are written as 0, so that two dumps compare under any tolerance."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name in results[0]:
+        vals = [r[name] for r in results]
+        if torch.is_tensor(vals[0]):
+            a = torch.stack([v.detach().cpu() for v in vals]).numpy().astype(np.float32)
+        else:
+            a = np.asarray(vals, dtype=np.float64 if isinstance(vals[0], int) else np.float32)
+        if name == "deltas":
+            a = np.nan_to_num(a, nan=0.0)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def main():
@@ -763,6 +804,8 @@ def main():
     eng, ctl, T = res["eng"], res["ctl"], res["T"]
     eng_ctl_max = eng.ctl_max_layer
     t_max, value = res["t_max"], res["value"]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res["last"], args.dump_outputs)
 
     out = {
         "metric": "action-steps/sec (whole job) + avg exit-layer, %s max_layer=%d, synthetic CALVIN-D-shaped inputs"
@@ -791,9 +834,11 @@ def main():
                    "envs_per_gpu": B, "ms_per_env_step": round(1e3 * t_max / (res["n_timed"] * B), 4),
                    "exit_hist": res["hist"] if world == 1 else None, "per_gpu_steps_per_s": round(value / world, 2),
                    "graph": not args.no_graph, "weights_gb": round(eng.weight_bytes() / 1e9, 3),
-                   "thresholds": [round(x, 6) for x in ctl.threshold_list()], "setup_s": round(res["setup_s"], 1),
-                   "calibration": "reference protocol, deterministic: %d shadow steps, LSTM history on a seeded random exit layer per "
-                                  "step, thresholds from solve_thresholds(exit_ratio=%.2f) (value_net.py:203-260)" % (args.calib_steps, args.exit_ratio),
+                   "thresholds": [round(x, 6) for x in ctl.threshold_list()] if res["thr"] is not None else None,
+                   "setup_s": round(res["setup_s"], 1),
+                   "calibration": ("reference protocol, deterministic: %d shadow steps, LSTM history on a seeded random exit layer per "
+                                   "step, thresholds from solve_thresholds(exit_ratio=%.2f) (value_net.py:203-260)" % (args.calib_steps, args.exit_ratio))
+                                  if res["thr"] is not None else "not run (scripted verdicts need no thresholds; --full calibrates)",
                    "timed_window": "%d warm-up steps, then %d timed steps of %d-step episodes" % (args.warmup, res["n_timed"], EP_LEN)},
         "lib_sha256_16": lib_hash(), "kernel_source_hash": kernel_source_hash(),
     }
@@ -822,7 +867,7 @@ def main():
         out["distinct_devices"] = len({r["device_uuid"] or r["device"] for r in out["ranks"]})
         out["per_rank_steps_per_s"] = res.get("rank_rate")
     # step latency at a KNOWN depth: static exit at every exit layer (median of --latency-reps steps, action read on the host)
-    if args.latency_reps > 0 and B == 1 and rank == 0:
+    if args.full and args.latency_reps > 0 and B == 1 and rank == 0:
         frames_, ids_l = res["frames"], res["ids"]
         lat = {}
         for e in [x for x in cfg.exit_ids() if x <= eng.ctl_max_layer]:
@@ -856,7 +901,7 @@ def main():
         out["value_at_target_depth"] = {"value": out["value"], "unit": "action-steps/s", "avg_exit_layer": out["avg_exit_layer"],
                                         "note": "= `value` since round 4: the timed region itself runs the target mix (kept for run-to-run "
                                                 "comparison with rounds 1-3, where it was the static-exit schedule now under `scripted`)"}
-    if args.scripted_steps > 0 and B == 1 and max_layer == 12:
+    if args.full and args.scripted_steps > 0 and B == 1 and max_layer == 12:
         exits = [e for e in cfg.exit_ids() if e <= eng.ctl_max_layer]
         sched = [exits[k] for k in target_schedule(len(exits), args.exit_ratio, args.scripted_steps, seed=99)]
         frames, ids_ = res["frames"], res["ids"]
@@ -883,16 +928,16 @@ def main():
                                    "id, no exit checks, host reads the action after every step"}
     if os.environ.get("DEER_PERSISTENT_LAYER") == "1":     # N1 experiment: never the default; say so on the line
         out["experiment"] = {"persistent_layer": True, "barrier_error_word": eng.persistent_layer_error(), "first_timeout": eng.persistent_layer_error_detail()}
-    if rank == 0 and world == 1 and B == 1 and args.surface_steps > 0 and args.precision != "fp32":
+    if args.full and rank == 0 and world == 1 and B == 1 and args.surface_steps > 0 and args.precision != "fp32":
         try:                                               # auxiliary single-rank leg: its failure must not cost the bench line
             out["surface"] = surface_leg(cfg, eng, res["thr"], res["frames"], res["ids"], args.surface_steps)
         except Exception as e:
             out["surface"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0 and not args.no_roofline:
+    if args.full and rank == 0 and not args.no_roofline:
         out["roofline"] = measure_roofline(eng, cfg, res["frames"], res["ids"], traffic_key="%s/envs%d" % (args.workload, B))
     # ---- the same workload with one ENV BATCH per rank (north_star: "one env batch per rank"): every weight byte and
     #      every kernel boundary is shared by the environments of the batch.  Reported beside `value`, never as it. ----
-    if args.batched_envs > 1 and B == 1:
+    if args.full and args.batched_envs > 1 and B == 1:
         del eng
         res["eng"] = None
         torch.cuda.empty_cache()
@@ -931,7 +976,7 @@ def main():
             except Exception as e:
                 out["batched_max_envs"] = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        if not (args.no_cpu_baseline or world > 1):
+        if args.full and not (args.no_cpu_baseline or world > 1):
             cb = cpu_baseline(cfg, sd, ctl, None, args.cpu_budget_s, args.cpu_threads, rank, full_protocol=args.cpu_full_protocol)
             out["cpu_baseline"] = cb
         print(json.dumps(out))

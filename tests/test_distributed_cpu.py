@@ -148,7 +148,7 @@ def test_bench_with_eight_ranks_through_torch_distributed_run():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr", "127.0.0.1", "--master-port",
            str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "6", "--warmup", "2", "--workload", "tiny", "--calib-steps", "24",
            "--burn-in", "0", "--on-policy-steps", "6", "--scripted-steps", "0", "--latency-reps", "0", "--no-cpu-baseline", "--batched-envs", "0",
-           "--surface-steps", "0", "--no-roofline"]
+           "--surface-steps", "0", "--no-roofline", "--full"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

@@ -12,7 +12,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 # whole bench under the kernel trace (every leg)
-BENCH="python $ROOT/bench.py --steps 100 --warmup 10 --no-cpu-baseline --batched-envs 0 --surface-steps 0"
+BENCH="python $ROOT/bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --batched-envs 0 --surface-steps 0"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- $BENCH > $OUT/trace_bench.json 2> $OUT/trace.err
 find $OUT/trace -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/kernel_stats_whole_bench.csv
 ARGS=""
