@@ -756,7 +756,7 @@ __global__ __launch_bounds__(256) void mpt_attn_small_kernel(const float* __rest
     for (int j = 0; j <= t; ++j) a += sim[t][j] * vs[j][d];
     if (out_is_f32) reinterpret_cast<float*>(out)[(long)t * ldo + h * hd + d] = a;
     else {
-      const bf16_t hi = f2x<F16>(a);
+      const bf16_t hi = f2x<F16>((F16 && out_lo != nullptr) ? f16_sat(a) : a);                    // fp16 pair: hi saturates (common.h: split2)
       reinterpret_cast<bf16_t*>(out)[(long)t * ldo + h * hd + d] = hi;
       if (out_lo != nullptr) out_lo[(long)t * ldo + h * hd + d] = f2x<F16>(a - x2f<F16>(hi));    // second plane: a = hi + lo
     }

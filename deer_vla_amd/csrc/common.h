@@ -88,9 +88,14 @@ template <bool F16> __device__ __forceinline__ f32x4 mfma16(bf16x8 a, bf16x8 b, 
   else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
 }
 // hi / lo split of two f32 values: hi = fmt(v), lo = fmt(v - hi) - the LLM trunk feeds every MFMA with both planes (two MFMAs per weight
-// fragment), so the activation side of a product carries ~16 (bf16) / ~22 (fp16) significand bits
+// fragment), so the activation side of a product carries ~16 (bf16) / ~22 (fp16) significand bits.
+// fp16: a finite |v| >= 65520 would round hi to +-inf and lo to -+inf (w*inf + w*(-inf) = NaN in the MFMA pair), so hi saturates at +-65504
+// and lo = fmt(v - hi) carries the rest (exact to 1/2 ulp of lo up to |v| ~ 1.3e5; beyond, lo = +-inf and hi + lo = +-inf as .half()
+// gives).  Below 65520 the clamp is the identity on hi (65504 < |v| < 65520 rounds to 65504 anyway), so those results keep their bits;
+// NaN fails both comparisons and stays NaN.
+__device__ __forceinline__ float f16_sat(float v) { return v > 65504.f ? 65504.f : (v < -65504.f ? -65504.f : v); }
 template <bool F16> __device__ __forceinline__ void split2(float a, float b, uint32_t& hi, uint32_t& lo) {
-  hi = pack2x<F16>(a, b);
+  hi = F16 ? pack2h(f16_sat(a), f16_sat(b)) : pack2bf(a, b);
   float ha, hb;
   if constexpr (F16) { ha = h2f((bf16_t)(hi & 0xffffu)); hb = h2f((bf16_t)(hi >> 16)); }
   else { ha = __uint_as_float(hi << 16); hb = __uint_as_float(hi & 0xffff0000u); }

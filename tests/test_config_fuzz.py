@@ -95,9 +95,29 @@ def batch_tensors(env_inputs, s, B):
 
 @pytest.mark.parametrize("case", range(N_CASES))
 def test_random_combination_of_variants_matches_the_oracle(case):
+    _run_case(case, *draw(case))
+
+
+# the same combinations on the MPT-7B / OpenFlamingo-9B trunk shape (no q/k LayerNorm, bias-free LayerNorms, gated x-attn in front of every
+# 4th layer); in half of the cases the thresholds come from the product's own solver with the 9B rule (no exit at the first exit point,
+# value_net.py:235-236): the engine then steps with the never-fire first threshold
+N_9B_CASES = int(os.environ.get("DEER_FUZZ_9B_CASES", "16"))
+MPT_9B_SHAPE = dict(llm_name="mpt_9b", attn_qk_ln=False, cross_attn_every_n_layers=4)
+
+
+@pytest.mark.parametrize("case", range(N_9B_CASES))
+def test_random_combination_on_the_mpt7b_trunk_shape_matches_the_oracle(case):
+    kw, *rest = draw(20000 + case)                               # a seed range of its own: draw()'s first cases keep their meaning
+    r = random.Random(30000 + case)
+    solver_ratio = r.choice([0.6, 0.8, 0.9]) if r.random() < 0.5 else None
+    _run_case(20000 + case, dict(kw, **MPT_9B_SHAPE), *rest, solver_ratio=solver_ratio)
+
+
+def _run_case(case, kw, B, precision, lens, ttype, wseed, sps, cut, solver_ratio=None):
+    """one drawn combination against the oracle; solver_ratio: thresholds from ExitController.set_threshold_from_values(deltas of a
+    never-exit episode, solver_ratio, "mpt_9b") instead of the widest gaps"""
     from deer_vla_amd import factory
     from deer_vla_amd.value_net import ActionValueNet, ExitController
-    kw, B, precision, lens, ttype, wseed, sps, cut = draw(case)
     precision = os.environ.get("DEER_FUZZ_PRECISION", precision)   # re-run a case in another arithmetic: is a miss the format or a bug?
     cfg = deer_tiny(**kw)
     A = cfg.multi_step_action
@@ -112,7 +132,8 @@ def test_random_combination_of_variants_matches_the_oracle(case):
     state = torch.randn(n_steps, 1, 1, 1, 15, generator=g)
     state[..., -1] = torch.where(torch.rand(n_steps, 1, 1, 1, generator=g) < 0.5, -1.0, 1.0)
     model, _, _ = factory.create_model_and_transforms(
-        "ViT-L-14", "openai", "", "", cross_attn_every_n_layers=1, window_size=12, use_gripper=True, fusion_mode=cfg.fusion_mode, llm_name="mpt_dolly_3b",
+        "ViT-L-14", "openai", "", "", cross_attn_every_n_layers=cfg.cross_attn_every_n_layers, window_size=12, use_gripper=True, fusion_mode=cfg.fusion_mode,
+        llm_name=cfg.llm_name,
         state_dict=sd, cfg=cfg, use_state=cfg.use_state, sep_resampler=cfg.sep_resampler, multi_step_action=A,
         layerwise_exit_eval=cfg.layerwise_exit_eval, multi_exit=cfg.layerwise_exit_eval, n_envs=B, precision=precision)
     exit_ids = cfg.exit_ids()
@@ -141,13 +162,27 @@ def test_random_combination_of_variants_matches_the_oracle(case):
     # ---- thresholds in the widest gaps of environment 0's never-exit deltas; then every environment's own oracle episode ----
     real = orc.OracleExitController(None, exit_ids, max_layer=max_layer).real_num_exit
     _, rec = oracle_dynamic(cfg, sd, env_inputs[0], [-1.0 if ttype != "cosine" else -3.0] * real, ttype, max_layer=max_layer)
-    thr = [gap_threshold([v for (i, v) in rec if i == e]) for e in exit_ids[:real]]
-    thr[-1] = 1e5
-    refs = [oracle_dynamic(cfg, sd, env_inputs[e], thr, ttype, 3e-4 if precision != "fp32" else 2e-5, sps, max_layer)[0] for e in range(B)]
-
     vn = ActionValueNet(model.get_all_exit_idx(), model.extra_exit, cfg.exit_interval, cfg.window_size, ttype)
     ctl = ExitController(vn, model.get_all_exit_idx(), steps_per_stage=sps, leq=True, exit_dist="exp", max_layer=max_layer)
+    if solver_ratio is None:
+        thr = [gap_threshold([v for (i, v) in rec if i == e]) for e in exit_ids[:real]]
+        thr[-1] = 1e5
+    else:
+        # calibration: the never-exit deltas of episodes the test does not replay (so no threshold sits exactly on a tested delta)
+        assert cfg.llm_name == "mpt_9b"
+        cal = []
+        for c in range(2):
+            cal_inputs = [syn.synthetic_step_inputs(cfg, 20 + s, rank=5 + c, text_len=lens[0], text_seed=wseed % 89 + 40 + c) for s in range(n_steps)]
+            cal += oracle_dynamic(cfg, sd, cal_inputs, [-1.0 if ttype != "cosine" else -3.0] * real, ttype, max_layer=max_layer)[1]
+        per_exit = [[v for (i, v) in cal if i == e] for e in exit_ids[:real]]
+        n = min(len(v) for v in per_exit)
+        ctl.set_threshold_from_values(torch.tensor([v[:n] for v in per_exit]), solver_ratio, cfg.llm_name)
+        thr = list(ctl.thresholds.values())
+        assert len(thr) == real and thr[0] == -1e8, thr          # the 9B rule: the first exit never fires
+    refs = [oracle_dynamic(cfg, sd, env_inputs[e], thr, ttype, 3e-4 if precision != "fp32" else 2e-5, sps, max_layer)[0] for e in range(B)]
     ctl._set_threshold_value(thr)
+    desc = desc + (solver_ratio, thr)
+    got_exits = []
     model.clear_all_exit_memory()
     alive, compared, seen, flips = [True] * B, 0, set(), 0
     for s in range(n_steps):
@@ -161,6 +196,7 @@ def test_random_combination_of_variants_matches_the_oracle(case):
             rgb, grip, ids, mask = batch_tensors(env_inputs, s, B)
             pose, gr, exits = model.step_env_batch(rgb.cuda(), ids.cuda(), mask.cuda(), grip.cuda(), exit_controller=ctl)
             got = [(exits[e], pose[e].cpu().reshape(-1), gr[e].cpu().reshape(-1)) for e in range(B)]
+        got_exits += [g[0] for g in got]
         for e in range(B):
             if not alive[e]:
                 continue
@@ -175,6 +211,8 @@ def test_random_combination_of_variants_matches_the_oracle(case):
             compared += 1
             seen.add(ex)
     assert compared >= 0.6 * B * n_steps or (flips and compared >= 1), (desc, compared, flips)
+    if solver_ratio is not None:                                  # neither side ever exits at the never-fire first exit
+        assert exit_ids[0] not in got_exits and all(ref[s][0] != exit_ids[0] for ref in refs for s in range(n_steps)), (desc, got_exits)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -492,6 +492,55 @@ def test_eight_environments_with_instructions_up_to_32_tokens():
     assert compared >= 0.8 * B * n_steps, (compared, flips)
 
 
+def _mpt7b_tiny():
+    return deer_tiny(llm_name="mpt_9b", attn_qk_ln=False, cross_attn_every_n_layers=4, n_layers_total=12, early_exit_layer=9)
+
+
+@pytest.mark.parametrize("precision", ["fp16", "bf16"])
+@pytest.mark.parametrize("B,sps", [(2, 1), (4, 1), (8, 1), (16, 2)])
+def test_mpt7b_shaped_env_batch_matches_independent_oracle_runs(B, sps, precision):
+    """The env batch on the MPT-7B / OpenFlamingo-9B trunk shape (no q/k LayerNorm, bias-free LayerNorms, x-attn in front of every 4th
+    layer): every environment against its own independent single-environment oracle run, in both 16-bit arithmetics."""
+    cfg = _mpt7b_tiny()
+    sd = syn.make_synthetic_state(cfg, 7, bf16_round=True)
+    eng = DeerEngine(cfg, sd, n_envs=B, precision=precision)
+    n_steps, T = 12, 9
+    env_inputs = [[syn.synthetic_step_inputs(cfg, s, rank=e, text_len=T, text_seed=7 + e) for s in range(n_steps)] for e in range(B)]
+    thr, _ = probe_thresholds(cfg, sd, env_inputs[0], 12, sps)
+    compared, flips, seen = run_env_batch_against_independent_oracles(cfg, sd, eng, env_inputs, thr, sps, n_steps, B)
+    assert compared >= 0.8 * B * n_steps, (compared, flips)
+    assert len(seen) > 1
+
+
+def test_mpt7b_shaped_env_batch_with_instructions_up_to_32_tokens():
+    """8 environments x up to 32 tokens (256 trunk rows: deer_gemm_skinny_hl_rows) on the MPT-7B trunk shape, mixed lengths, each
+    environment against its own UNPADDED oracle run"""
+    cfg = _mpt7b_tiny()
+    sd = syn.make_synthetic_state(cfg, 7, bf16_round=True)
+    B, n_steps = 8, 6
+    lens = [32, 14, 20, 9, 27, 16, 31, 11]
+    eng = DeerEngine(cfg, sd, n_envs=B)
+    assert eng.max_rows == 256
+    env_inputs = [[syn.synthetic_step_inputs(cfg, s, rank=e, text_len=lens[e], text_seed=7 + e) for s in range(n_steps)] for e in range(B)]
+    thr, _ = probe_thresholds(cfg, sd, env_inputs[0], 12, 1)
+    compared, flips, seen = run_env_batch_against_independent_oracles(cfg, sd, eng, env_inputs, thr, 1, n_steps, B)
+    assert compared >= 0.8 * B * n_steps, (compared, flips)
+
+
+def test_mpt7b_shaped_env_batch_with_staggered_sub_tasks():
+    """steps_per_stage = 3 with sub-tasks restarting at different batch steps (per-environment stage hold) on the MPT-7B trunk shape"""
+    cfg = _mpt7b_tiny()
+    sd = syn.make_synthetic_state(cfg, 7, bf16_round=True)
+    B, sps, restarts = 4, 3, [None, 4, 5, 7]
+    eng = DeerEngine(cfg, sd, n_envs=B)
+    n_steps, T = 14, 9
+    env_inputs = [[syn.synthetic_step_inputs(cfg, s, rank=e, text_len=T, text_seed=7 + e) for s in range(n_steps)] for e in range(B)]
+    thr, _ = probe_thresholds(cfg, sd, env_inputs[0], 12, sps)
+    compared, flips, seen = run_env_batch_against_independent_oracles(cfg, sd, eng, env_inputs, thr, sps, n_steps, B, restarts)
+    assert compared >= 0.8 * B * n_steps, (compared, flips)
+    assert len(seen) > 1
+
+
 def test_full_size_mpt1b_vitl14_steps_vs_oracle():
     """BASELINE config sizes (ViT-L/14 x2, Perceiver, MPT-1B d=2048 x12 layers, 4x1024 LSTM head): static exit
     and a short dynamic episode against the fp32 CPU oracle."""
@@ -554,10 +603,19 @@ def test_full_size_mpt7b_openflamingo9b_steps_vs_oracle():
     """BASELINE configs[4] at FULL size (MPT-7B trunk: d=4096, 32 heads x 128, FF 16384, gated x-attn in front of every 4th
     layer, no q/k LayerNorm; 13 layers for max_layer=12): hidden states, static exits and a dynamic episode (pipelined
     schedule included) against the fp32 CPU oracle."""
+    _full_size_9b_vs_oracle("fp16")
+
+
+def test_full_size_mpt7b_openflamingo9b_steps_vs_oracle_bf16():
+    """the same in the bf16 arithmetic (BASELINE config 5); the oracle's trunk memo makes this arm cost engine time only"""
+    _full_size_9b_vs_oracle("bf16")
+
+
+def _full_size_9b_vs_oracle(precision):
     from deer_vla_amd.config import deer_9b
     cfg = deer_9b(max_layer=12)
     sd = syn.make_synthetic_state(cfg, 0, std="0.02", bf16_round=True)
-    eng = DeerEngine(cfg, sd)
+    eng = DeerEngine(cfg, sd, precision=precision)
     inputs = make_inputs(cfg, 4)
     model = orc.OracleDeer(sd, cfg)
     model.set_all_exit_window_size(1)
@@ -582,6 +640,73 @@ def test_full_size_mpt7b_openflamingo9b_steps_vs_oracle():
             assert rr["exit_layer"] == ref[s][0], (use_graph, s, rr["exit_layer"], ref[s][0], rr["deltas"][:7], thr)
             assert float((rr["pose"] - ref[s][1]).abs().max()) < ACTION_TOL
 
+
+def test_full_size_mpt7b_openflamingo9b_env_batch_vs_oracle_and_compaction():
+    """The MPT-7B / OpenFlamingo-9B trunk at FULL size (d = 4096, 32 heads) with FOUR environments in one engine: static exits at the last
+    layer and at an exit layer (LSTM carried from the first), every environment against its own fp32 oracle (hidden states of layers 0, 3,
+    7 and the last, actions); then a short dynamic episode with compaction on, bit-identical to a compaction-off sibling engine."""
+    from deer_vla_amd.config import deer_9b
+    cfg = deer_9b(max_layer=12)
+    sd = syn.make_synthetic_state(cfg, 0, std="0.02", bf16_round=True)
+    B, T, n_steps = 4, 14, 3
+    eng = DeerEngine(cfg, sd, n_envs=B)
+    env_inputs = [[syn.synthetic_step_inputs(cfg, s, rank=e, text_len=T, text_seed=7 + e) for s in range(n_steps)] for e in range(B)]
+    rgb = torch.stack([env_inputs[e][0][0] for e in range(B)])
+    grip = torch.stack([env_inputs[e][0][1] for e in range(B)])
+    ids = torch.cat([env_inputs[e][0][2] for e in range(B)])
+    last = cfg.n_layers - 1
+    mid = 7 if 7 in cfg.exit_ids() else cfg.exit_ids()[len(cfg.exit_ids()) // 2]
+    models = [orc.OracleDeer(sd, cfg) for _ in range(B)]
+    for m in models:
+        m.set_all_exit_window_size(1)
+    eng.reset()
+    for k, exit_id in enumerate((last, mid)):                   # the same frame twice: the second step carries the first one's LSTM state
+        out = eng.step(rgb, grip, ids, None, exit_id=exit_id, use_graph=False)
+        assert len(out) == B
+        for e in range(B):
+            r_e, g_e, i_e, m_e = env_inputs[e][0]
+            o = models[e].forward(r_e, i_e, m_e, g_e, exit_id=exit_id)
+            assert out[e]["exit_layer"] == exit_id
+            if k == 0:
+                for i in (0, 3, 7, last):                      # 3, 7: layers with a gated x-attn block in front
+                    a, b = eng.hidden[i, e * T:(e + 1) * T].cpu(), o["hidden_states"][i][0]
+                    assert float((a - b).norm() / b.norm()) < 2e-2, (e, i)
+            assert float((out[e]["pose"] - o["logits"][0].reshape(-1)).abs().max()) < ACTION_TOL, (e, exit_id)
+            assert abs(out[e]["gripper"] - float(o["logits"][1])) < ACTION_TOL, (e, exit_id)
+    # dynamic episode: compaction on vs off (thresholds = per-exit median of a shadow step's deltas: the environments leave at different layers)
+    eng_off = DeerEngine(cfg, None, n_envs=B, weights_from=eng)
+    eng_off.set_compaction(False)
+    exit_ids = cfg.exit_ids()
+    eng_off.configure_exit(exit_ids, 12, 1)
+    real = eng_off.real_num_exit                                  # exits up to max_layer = 12
+    eng_off.set_thresholds([1e-9] * (real - 1) + [1e5])
+    eng_off.reset()
+    rec = [[] for _ in range(real)]
+    for s in range(n_steps):
+        rgb = torch.stack([env_inputs[e][s][0] for e in range(B)]).cuda().to(eng.img_dtype)
+        grip = torch.stack([env_inputs[e][s][1] for e in range(B)]).cuda().to(eng.img_dtype)
+        for r in eng_off.step(rgb, grip, ids, None, use_graph=False, shadow=True):
+            for k in range(real):
+                rec[k].append(float(r["deltas"][k]))
+    thr = [float(np.median(v)) for v in rec[:-1]] + [1e5]
+    for en in (eng, eng_off):
+        en.configure_exit(exit_ids, 12, 1)
+        en.set_thresholds(thr)
+        en.reset()
+    seen = set()
+    for s in range(n_steps):
+        rgb = torch.stack([env_inputs[e][s][0] for e in range(B)]).cuda().to(eng.img_dtype)
+        grip = torch.stack([env_inputs[e][s][1] for e in range(B)]).cuda().to(eng.img_dtype)
+        ra = eng.step(rgb, grip, ids, None, use_graph=(s >= 1))
+        rb = eng_off.step(rgb, grip, ids, None, use_graph=(s >= 1))
+        for e in range(B):
+            assert ra[e]["exit_layer"] == rb[e]["exit_layer"], (s, e)
+            assert torch.equal(ra[e]["pose"], rb[e]["pose"]) and ra[e]["gripper"] == rb[e]["gripper"], (s, e)
+            assert torch.equal(torch.nan_to_num(ra[e]["deltas"], nan=-1.0), torch.nan_to_num(rb[e]["deltas"], nan=-1.0)), (s, e)
+            seen.add(ra[e]["exit_layer"])
+        torch.cuda.synchronize()
+        assert torch.equal(eng.h_state, eng_off.h_state) and torch.equal(eng.c_state, eng_off.c_state), s
+    assert len(seen) > 1, seen                                    # environments left at different layers: rows were compacted
 
 
 def _window_reference(cfg, sd, frames, W):
@@ -641,13 +766,22 @@ def test_window_mode_calibration_full_size_batched_vs_oracle(max_layer):
     """the 12-frame history window as batch rows at FULL size (ViT at M = 8*514 rows, trunk at 112 rows):
     calibration deltas (value_net.py:134-160) of one 12-step window against the fp32 oracle.  max_layer = 4 is BASELINE configs[1]
     (DeeR-S, "12-step history": 5 layers built, exit ids {1, 3, 4})."""
+    _window_full_size_vs_oracle(max_layer, None)
+
+
+def test_window_mode_calibration_full_size_batched_vs_oracle_bf16():
+    """DeeR-S (max_layer = 4) of the test above in the bf16 arithmetic (same weights, same oracle reference)"""
+    _window_full_size_vs_oracle(4, "bf16")
+
+
+def _window_full_size_vs_oracle(max_layer, precision):
     cfg = deer_3b(max_layer=max_layer)
     # one weight set for both cases: every tensor is seeded by its NAME (synthetic.make_synthetic_state), so the five-layer DeeR-S model
     # is the first five layers of the twelve-layer one - and so are the oracle's hidden states, computed once for both
     cfg12 = deer_3b(max_layer=12)
     sd12 = full_size_state(cfg12, 0, std="0.02", bf16_round=True)
     sd = {k: sd12[k] for k in syn.param_shapes(cfg)}
-    eng = DeerEngine(cfg, sd)
+    eng = DeerEngine(cfg, sd, precision=precision)
     W = 12
     exit_ids = cfg.exit_ids()
     frames = [[syn.synthetic_step_inputs(cfg, 100 + t) for t in range(W)]]
@@ -690,6 +824,11 @@ def test_compaction_of_exited_environments_is_bit_identical_to_the_uncompacted_b
     verdict the stream has ordered (exit layer <= i - 2, csrc/resadd_body.h), else workgroups could disagree about the packing."""
     cfg = deer_tiny()
     sd = syn.make_synthetic_state(cfg, 3, bf16_round=True)
+    _compaction_vs_uncompacted(cfg, sd, B, lens, use_graph, exits)
+
+
+def _compaction_vs_uncompacted(cfg, sd, B, lens, use_graph, exits):
+    """the body of the compaction test above; returns the exit layers of every step (one list of B per step)"""
     n_steps = 10 if exits is None else 16
     lens = lens or [11] * B
     eng_on = DeerEngine(cfg, sd, n_envs=B)
@@ -705,7 +844,7 @@ def test_compaction_of_exited_environments_is_bit_identical_to_the_uncompacted_b
         ids[e, :lens[e]] = env_inputs[e][0][2].reshape(-1)
         mask[e, :lens[e]] = True
     ids, mask = ids.cuda(), mask.cuda()
-    seen = set()
+    seen, steps = set(), []
     if exits is not None:
         # thresholds of the denser exit list: the per-exit median of the deltas of a shadow episode (every exit evaluated, none taken) -
         # about half of the environments that reach an exit leave there, so ADJACENT layers both see exits
@@ -729,6 +868,7 @@ def test_compaction_of_exited_environments_is_bit_identical_to_the_uncompacted_b
         grip = torch.stack([env_inputs[e][s][1] for e in range(B)]).cuda().to(eng_on.img_dtype)
         ra = eng_on.step(rgb, grip, ids, mask if len(set(lens)) > 1 else None, use_graph=use_graph)
         rb = eng_off.step(rgb, grip, ids, mask if len(set(lens)) > 1 else None, use_graph=use_graph)
+        steps.append([ra[e]["exit_layer"] for e in range(B)])
         for e in range(B):
             assert ra[e]["exit_layer"] == rb[e]["exit_layer"], (s, e)
             assert torch.equal(ra[e]["pose"], rb[e]["pose"]) and ra[e]["gripper"] == rb[e]["gripper"], (s, e)
@@ -740,6 +880,22 @@ def test_compaction_of_exited_environments_is_bit_identical_to_the_uncompacted_b
     assert len(seen) > 1, seen                                    # environments really left at different layers
     if exits is not None:                                         # ... and at ADJACENT layers (the case the gather's rule exists for)
         assert any(l + 1 in seen for l in seen), seen
+    return steps
+
+
+@pytest.mark.parametrize("use_graph", [True, False])
+def test_compaction_in_the_mpt7b_shaped_trunk_is_bit_identical_to_the_uncompacted_batch(use_graph):
+    """The compaction test above on the MPT-7B / OpenFlamingo-9B trunk shape (no q/k LayerNorm, bias-free LayerNorms, gated x-attn only in
+    front of every 4th layer) with consecutive exits 1..7 (the last one always fires): every layer 3 .. 7 is a compaction layer; the
+    gathering row operation is the x-attn block's LayerNorm on layers 3 and 7 and the decoder's ln_1 (beta = NULL) on the others
+    (csrc/model.hip).  `gathers` = the layers on which a gather must have dropped rows (worked out from the exit layers of each step: an
+    environment that exited at l leaves at layer l + 2 if another one still runs it) - it must hold both kinds of layer."""
+    cfg = deer_tiny(llm_name="mpt_9b", attn_qk_ln=False, cross_attn_every_n_layers=4, n_layers_total=12, early_exit_layer=9)
+    sd = syn.make_synthetic_state(cfg, 7, bf16_round=True)
+    steps = _compaction_vs_uncompacted(cfg, sd, 8, None, use_graph, [1, 2, 3, 4, 5, 6, 7])
+    # a gather at layer i drops the environments that exited at layer i - 2 while another one still runs layer i
+    gathers = {l + 2 for ex in steps for l in ex if l + 2 <= max(ex)}
+    assert any(cfg.has_xattn(i) for i in gathers) and any(not cfg.has_xattn(i) for i in gathers), (gathers, steps)
 
 
 # the full-size variants of the two OFF-BY-DEFAULT experiments (one-launch head evaluation, persistent trunk layer) cost 40 s each:
