@@ -102,6 +102,8 @@ SIGNATURES = {
     "deer_head_fc": [P, I, I, I, P, P, P, P, P, P, P, P, I, P, I, F, P, I, I, I, P],
     "deer_head_final": [P, I, I, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P, P, P, I, I, I, P, F, I, P],
     "deer_head_final_multi": [P, I, I, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P, P, P, I, I, I, P, F, I, I, P, P],
+    "deer_head_final_env": [P, I, I, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P, P, P, I, I, I, P, F, I, I, P, P],
+    "deer_env_exit_write": [P, P, I, P, I, P],
     "deer_head_fused_granules": [I, I, I, I, I, P],
     "deer_head_fused": [P, I, I, P],
     "deer_ctl_begin_step": [P, P, I, P],
@@ -128,6 +130,10 @@ SIGNATURES = {
     "deer_model_set_head_fused": [P, I],
     "deer_model_head_state_changed": [P],
     "deer_model_set_persistent_layer": [P, I],
+    "deer_model_set_env_exit": [P, P, P, I, P],
+    "deer_model_set_env_exit_device": [P, P, P, I, P],
+    "deer_model_clear_env_exit": [P],
+    "deer_model_max_layer": [P],
     "deer_vit_l14_encode": [P, P, I, P, P],
     "deer_perceiver_resample": [P, P, I, P, P, P],
     "deer_llm_early_exit": [P, P, P, I, P, I, I, P, P, P],
@@ -177,6 +183,8 @@ def max_trunk_rows(cfg, precision: str = "fp16") -> int:
 
 
 MAX_ENVS = 16        # environments per engine (csrc/common.h: DEER_MAX_ENVS)
+ENV_EXIT_CAPS = MAX_ENVS * 16                   # per-environment operating points (csrc/common.h ENV_EXIT_*): rows [16][16] f32, then caps [16] int32
+ENV_EXIT_WORDS = MAX_ENVS * 16 + MAX_ENVS
 
 
 def skinny_mpad(M: int) -> int:

@@ -50,6 +50,11 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
 #define CMAP_ENV_SLOT 17     // up to 16 environments per engine (round 5)
 #define CMAP_WORDS 64
 #define DEER_MAX_ENVS 16
+// Per-environment exit operating points (one threshold row and one layer cap per environment): f32 rows [DEER_MAX_ENVS][16] (env b's
+// threshold of exit slot s at b * 16 + s), then int32 caps [DEER_MAX_ENVS] at word ENV_EXIT_CAPS (env b's check at layer >= cap b is
+// forced).  Device memory read at every exit check, so changing it needs no graph recapture.
+#define ENV_EXIT_CAPS (DEER_MAX_ENVS * 16)
+#define ENV_EXIT_WORDS (DEER_MAX_ENVS * 16 + DEER_MAX_ENVS)
 __device__ __forceinline__ int cmap_active(const int* cmap, int B) { return cmap != nullptr ? cmap[CMAP_N] : B; }
 __device__ __forceinline__ int cmap_env(const int* cmap, int slot) { return cmap != nullptr ? cmap[CMAP_SLOT_ENV + slot] : slot; }
 __device__ __forceinline__ int cmap_slot(const int* cmap, int env) { return cmap != nullptr ? cmap[CMAP_ENV_SLOT + env] : env; }

@@ -828,7 +828,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
                                                 float* __restrict__ c_state, int L, int H, int B,
                                                 float* __restrict__ action_dbg, float eps, int A,
                                                 float* __restrict__ act_ext, const unsigned long long* hgran,
-                                                const unsigned long long* cgran) {
+                                                const unsigned long long* cgran, const int* __restrict__ env_caps) {
   if (head_skip(ctl0, kind, layer, B)) {
     // Every workgroup of a CHECK launch reports exactly once, whatever path it takes: a check nobody needed (stage hold)
     // still tells the host that this segment is over, and a workgroup that starts late may see ALL_EXITED raised by a
@@ -865,12 +865,16 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
   // thread 0's protocol section below reads LDS instead of walking a chain of dependent L2 round trips, and the host mirror leaves as
   // ONE wave store of the staged block (it used to be 64 serial loads + stores to host memory: 7.3 us of every committing evaluation)
   __shared__ int sctl[CTL_WORDS];
+  // env_caps != NULL: per-environment operating points (common.h ENV_EXIT_*) - thresholds is the [B][16] table, this environment's row
+  // and its layer cap are staged instead of the shared row and the engine-wide force flag
   __shared__ float sthr;
-  __shared__ int sshadow;
+  __shared__ int sshadow, sforce;
   if (wave == 7 && ctl != nullptr) {
     sctl[lane] = ctl[lane];
     if (lane == 0) {
-      sthr = (kind == KIND_CHECK && thresholds != nullptr && slot >= 0) ? thresholds[slot] : 0.f;
+      const int ti = env_caps != nullptr ? b * 16 + slot : slot;
+      sthr = (kind == KIND_CHECK && thresholds != nullptr && slot >= 0) ? thresholds[ti] : 0.f;
+      sforce = (force != 0 || (env_caps != nullptr && layer >= env_caps[b])) ? 1 : 0;
       sshadow = ctl0[CTL_SHADOW];
     }
   }
@@ -968,8 +972,8 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
         reinterpret_cast<float*>(ctl + CTL_ENS_ACTION)[7] = two ? 2.f : 1.f;
         ctl[CTL_PREV_REAL] = 1;
         for (int i = 0; i < NA; ++i) prev[i] = outv[i];
-        const bool below = delta <= thresholds[slot];
-        if ((below == (leq != 0)) || force) {
+        const bool below = delta <= sthr;
+        if ((below == (leq != 0)) || sforce) {
           ctl[CTL_CUR_EXIT_ID] = layer;
           commit = true;
         }
@@ -1059,7 +1063,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
           }
           for (int i = 0; i < 8; ++i) wf(CTL_PREV_ACTION + i, cur[i]);   // action_list.append(action)
           const bool below = delta <= sthr;
-          if ((below == (leq != 0)) || force) {           // value_net.py:293
+          if ((below == (leq != 0)) || sforce) {          // value_net.py:293
             wi(CTL_CUR_EXIT_ID, layer);
             commit = true;
           }
@@ -1160,14 +1164,14 @@ __global__ __launch_bounds__(512) void head_final_kernel(const float* __restrict
                                                          const float* __restrict__ c_tmp, float* __restrict__ h_state,
                                                          float* __restrict__ c_state, int L, int H, int B,
                                                          float* __restrict__ action_dbg, float eps, int A,
-                                                         float* __restrict__ act_ext) {
+                                                         float* __restrict__ act_ext, const int* __restrict__ env_caps) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int b = blockIdx.x;
   const bool grouped = (pro == PRO_GROUP_LN_RELU || pro == PRO_GROUP_RELU);
   const float* s0 = src + (long)b * src_stride;
   const float* s1 = s0 + (grouped ? in_dim : 0);
   head_final_body<WT, false>(b, s0, s1, lds, in_dim, pro, lnw0, lnb0, lnw1, lnb1, Wa, ba, Wg, bg, ctl0, kind, layer, slot, thresholds, force,
-                             thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, nullptr, nullptr);
+                             thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, nullptr, nullptr, env_caps);
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -1591,7 +1595,7 @@ __global__ __launch_bounds__(512) void head_fused_kernel(deer_head_fused_args a)
   HF_STAMP();                                                        // final input gathered
   head_final_body<WT, true>(b, s0, s1, xs, in_dim, pro, lw0, lb0, lw1, lb1, reinterpret_cast<const WT*>(a.Wa), a.ba, reinterpret_cast<const WT*>(a.Wg),
                             a.bg, ctl0, a.kind, a.layer, a.slot, a.thresholds, a.force, a.thr_type, a.leq, a.h_tmp, a.c_tmp, a.h_state, a.c_state, L,
-                            H, B, a.action_dbg, a.eps, a.A, a.act_ext, gH, gC);
+                            H, B, a.action_dbg, a.eps, a.A, a.act_ext, gH, gC, nullptr);   // shared row only (the model refuses a per-env table here)
   __syncthreads();
   HF_STAMP();                                                        // done
   if (b == 0 && threadIdx.x == 0) ((volatile unsigned*)a.err)[1] = tag;      // one environment: workgroup 0 is the only one that gets here
@@ -1662,25 +1666,70 @@ extern "C" int deer_head_final(const float* src, int src_stride, int in_dim, int
                                thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, w_is_f32, 1, nullptr, stream);
 }
 
-extern "C" int deer_head_final_multi(const float* src, int src_stride, int in_dim, int pro, const float* lnw0, const float* lnb0,
-                                     const float* lnw1, const float* lnb1, const void* Wa, const float* ba, const void* Wg, const float* bg,
-                                     int* ctl, int kind, int layer, int slot, const float* thresholds, int force, int thr_type, int leq,
-                                     const float* h_tmp, const float* c_tmp, float* h_state, float* c_state, int L, int H, int B,
-                                     float* action_dbg, float eps, int w_is_f32, int A, float* act_ext, void* stream) {
+static int head_final_launch(const float* src, int src_stride, int in_dim, int pro, const float* lnw0, const float* lnb0, const float* lnw1,
+                             const float* lnb1, const void* Wa, const float* ba, const void* Wg, const float* bg, int* ctl, int kind, int layer,
+                             int slot, const float* thresholds, const int* env_caps, int force, int thr_type, int leq, const float* h_tmp,
+                             const float* c_tmp, float* h_state, float* c_state, int L, int H, int B, float* action_dbg, float eps, int w_is_f32,
+                             int A, float* act_ext, void* stream) {
   if (in_dim <= 0 || (in_dim & 7) || pro < 0 || pro > 3 || kind < 0 || kind > 2 || B <= 0 || B > DEER_MAX_ENVS) return DEER_ERR_SHAPE;
   if (kind == KIND_CHECK && (thresholds == nullptr || slot < 0 || ctl == nullptr)) return DEER_ERR_SHAPE;
+  if (env_caps != nullptr && (thresholds == nullptr || slot >= 16)) return DEER_ERR_SHAPE;   // rows of 16 exit slots
   if (A < 1 || A > 8 || (A > 1 && ctl != nullptr && act_ext == nullptr)) return DEER_ERR_SHAPE;
   const int smem = (2 * in_dim + 16 + 64 + 4) * (int)sizeof(float);
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (w_is_f32 == 1) hipLaunchKernelGGL(head_final_kernel<float>, dim3(B), dim3(512), smem, st, src, src_stride, in_dim, pro, lnw0, lnb0, lnw1, lnb1,
                        reinterpret_cast<const float*>(Wa), ba, reinterpret_cast<const float*>(Wg), bg, ctl, kind, layer, slot,
-                       thresholds, force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext);
+                       thresholds, force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, env_caps);
     else if (w_is_f32 == 2) hipLaunchKernelGGL(head_final_kernel<half_t>, dim3(B), dim3(512), smem, st, src, src_stride, in_dim, pro, lnw0, lnb0, lnw1, lnb1,
                        reinterpret_cast<const half_t*>(Wa), ba, reinterpret_cast<const half_t*>(Wg), bg, ctl, kind, layer, slot,
-                       thresholds, force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext);
+                       thresholds, force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, env_caps);
     else hipLaunchKernelGGL(head_final_kernel<bf16_t>, dim3(B), dim3(512), smem, st, src, src_stride, in_dim, pro, lnw0, lnb0, lnw1, lnb1,
                        reinterpret_cast<const bf16_t*>(Wa), ba, reinterpret_cast<const bf16_t*>(Wg), bg, ctl, kind, layer, slot,
-                       thresholds, force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext);
+                       thresholds, force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, env_caps);
+  DEER_LAUNCH_CHECK();
+  return DEER_OK;
+}
+
+extern "C" int deer_head_final_multi(const float* src, int src_stride, int in_dim, int pro, const float* lnw0, const float* lnb0,
+                                     const float* lnw1, const float* lnb1, const void* Wa, const float* ba, const void* Wg, const float* bg,
+                                     int* ctl, int kind, int layer, int slot, const float* thresholds, int force, int thr_type, int leq,
+                                     const float* h_tmp, const float* c_tmp, float* h_state, float* c_state, int L, int H, int B,
+                                     float* action_dbg, float eps, int w_is_f32, int A, float* act_ext, void* stream) {
+  return head_final_launch(src, src_stride, in_dim, pro, lnw0, lnb0, lnw1, lnb1, Wa, ba, Wg, bg, ctl, kind, layer, slot, thresholds, nullptr, force,
+                           thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, w_is_f32, A, act_ext, stream);
+}
+
+// the same with a per-environment operating point: env_exit = the [ENV_EXIT_WORDS] table of common.h (env b's threshold row at b * 16,
+// the int32 layer caps at word ENV_EXIT_CAPS).  Environment b's check compares with its own row and is forced at layer >= its cap (or when
+// `force` is set).
+extern "C" int deer_head_final_env(const float* src, int src_stride, int in_dim, int pro, const float* lnw0, const float* lnb0,
+                                   const float* lnw1, const float* lnb1, const void* Wa, const float* ba, const void* Wg, const float* bg,
+                                   int* ctl, int kind, int layer, int slot, const float* env_exit, int force, int thr_type, int leq,
+                                   const float* h_tmp, const float* c_tmp, float* h_state, float* c_state, int L, int H, int B,
+                                   float* action_dbg, float eps, int w_is_f32, int A, float* act_ext, void* stream) {
+  if (env_exit == nullptr) return DEER_ERR_SHAPE;
+  return head_final_launch(src, src_stride, in_dim, pro, lnw0, lnb0, lnw1, lnb1, Wa, ba, Wg, bg, ctl, kind, layer, slot, env_exit,
+                           reinterpret_cast<const int*>(env_exit + ENV_EXIT_CAPS), force, thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B,
+                           action_dbg, eps, w_is_f32, A, act_ext, stream);
+}
+
+// writes the per-environment table: rows [n][16] f32 from the device (rows_dev) or by value (rows_val: the host copy travels in the
+// kernel arguments), caps [n] by value; one launch, ordered on `stream` behind the steps enqueued before it
+struct EnvExitVals { float rows[DEER_MAX_ENVS * 16]; int caps[DEER_MAX_ENVS]; };
+__global__ void env_exit_write_kernel(float* table, const float* rows_dev, EnvExitVals v, int n) {
+  const int i = threadIdx.x;
+  if (i < n * 16) table[i] = rows_dev != nullptr ? rows_dev[i] : v.rows[i];
+  if (i < n) reinterpret_cast<int*>(table + ENV_EXIT_CAPS)[i] = v.caps[i];
+}
+
+extern "C" int deer_env_exit_write(float* env_exit, const float* rows, int rows_on_device, const int* caps, int n_envs, void* stream) {
+  if (env_exit == nullptr || rows == nullptr || caps == nullptr || n_envs <= 0 || n_envs > DEER_MAX_ENVS) return DEER_ERR_SHAPE;
+  EnvExitVals v{};
+  if (!rows_on_device)
+    for (int i = 0; i < n_envs * 16; ++i) v.rows[i] = rows[i];
+  for (int i = 0; i < n_envs; ++i) v.caps[i] = caps[i];
+  hipLaunchKernelGGL(env_exit_write_kernel, dim3(1), dim3(DEER_MAX_ENVS * 16), 0, reinterpret_cast<hipStream_t>(stream), env_exit,
+                     rows_on_device ? rows : nullptr, v, n_envs);
   DEER_LAUNCH_CHECK();
   return DEER_OK;
 }

@@ -209,6 +209,9 @@ struct deer_model {
   // controller
   std::vector<int> exit_ids;
   int ctl_max_layer = 0, thr_type = 0, leq = 1;
+  int cfg_max_layer = 0;            // the cap deer_model_configure_exit derived (ctl_max_layer while no per-environment table is active)
+  size_t env_exit = SIZE_MAX;       // per-environment operating points (common.h ENV_EXIT_*): threshold row + layer cap of every environment
+  bool env_exit_on = false;         // deer_model_set_env_exit*: exit checks read env_exit; ctl_max_layer = the largest cap
   bool persistent_layer = false;    // N1 experiment: one launch per trunk layer (DEER_PERSISTENT_LAYER=1 / deer_model_set_persistent_layer)
   size_t ghh = 0;
   bool head_pre = true;             // recurrent half of the LSTM head once per control step (DEER_HEAD_PRE=0: every evaluation streams W_hh again)
@@ -628,6 +631,7 @@ void build_workspace(deer_model* m) {
     }
     m->ws_named["lw_state"] = {base, 2 * st * m->lw.size()};
   }
+  m->env_exit = named(m, "env_exit", ENV_EXIT_WORDS * 4);
 }
 
 // ---- launch helpers ---------------------------------------------------------------------------------------------------
@@ -1077,6 +1081,7 @@ int llm_layer_r16(deer_model* m, int i, int T, bool use_mask, bool pending_in, b
   long stride;
   // N1 experiment (csrc/persistent_layer.hip): the whole layer as ONE persistent launch - same device functions, same order, bit-identical
   // results, SLOWER; never the default (a persistent launch needs all of its workgroups resident: one engine per GPU)
+  if (m->persistent_layer && m->env_exit_on) return DEER_ERR_SHAPE;   // the experiment knows the shared operating point only
   if (m->persistent_layer && !m->f16 && L.has_xa && c.xattn_ff_mult == 4 && c.mlp_ratio == 4) {
     const XattnW& X = L.xa;
     deer_trunk_layer_args a{};
@@ -1310,6 +1315,9 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
   const bool feats_default = feats == nullptr;
   if (feats == nullptr) feats = m->Wk<float>(m->hidden) + (size_t)layer * rows_cap * d;     // [B*T, d]: env b owns rows b*T .. b*T+T-1
   const unsigned char* km = use_mask ? (m->mask_override ? m->mask_override : m->Wk<unsigned char>(m->key_mask)) : nullptr;
+  // a per-environment table: the one-launch evaluation and an explicit threshold row (deer_llm_early_exit) only know the shared row
+  const bool env_thr = m->env_exit_on && head == 0 && kind == DEER_KIND_CHECK && !no_ctl_final;
+  if (env_thr && (m->head_fused || m->thr_override != nullptr)) return DEER_ERR_SHAPE;
   // ---- control steps of one environment: the whole evaluation as ONE launch (csrc/head.hip: head_fused_kernel) ----
   if (m->head_fused && !m->f16 && head == 0 && use_ctl && !no_ctl_final && feats_default && kind != DEER_KIND_COMMIT && B == 1 && !c.precision && !c.use_state &&
       m->head_pre && m->ghh_valid && m->Lh <= 4 && m->n_fc <= 3 && d <= 2048 && H <= 1024) {
@@ -1398,6 +1406,11 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
     else { pro = DEER_PRO_GROUP_RELU; ln[0] = ln[1] = ln[2] = ln[3] = nullptr; }
   }
   Bracket b(m, "deer_head_final", 0, 0, st);
+  if (env_thr)
+    return deer_head_final_env(src, sstride, in_dim, pro, ln[0], ln[1], ln[2], ln[3], m->A<void>(wa), m->A<float>(ba), m->A<void>(wg), m->A<float>(bg),
+                               m->Wk<int>(m->ctl), kind, layer, slot, m->Wk<float>(m->env_exit), force ? 1 : 0, m->thr_type, m->leq, h_tmp, c_tmp,
+                               m->Wk<float>(shadow ? m->h_shadow : m->h_state), m->Wk<float>(shadow ? m->c_shadow : m->c_state), m->Lh, H, B,
+                               m->Wk<float>(m->action_dbg), kEps, m->wkind, std::max(1, c.multi_step_action), m->Wk<float>(m->act_ext), st);
   const float* thr = m->thr_override ? m->thr_override : m->Wk<float>(m->thresholds);
   return deer_head_final_multi(src, sstride, in_dim, pro, ln[0], ln[1], ln[2], ln[3], m->A<void>(wa), m->A<float>(ba), m->A<void>(wg), m->A<float>(bg),
                                no_ctl_final ? nullptr : m->Wk<int>(m->ctl), kind, layer, slot, thr, force ? 1 : 0, m->thr_type, m->leq, h_tmp, c_tmp,
@@ -1533,7 +1546,7 @@ int deer_model_create(const deer_config* cfg, deer_model** out) {
   // default controller: exits every exit_interval layers + the last layer (flamingo_mpt.py:239-250,268-270)
   for (int i = c.exit_interval - 1; i < c.n_layers - 1; i += c.exit_interval) m->exit_ids.push_back(i);
   m->exit_ids.push_back(c.n_layers - 1);
-  m->ctl_max_layer = m->exit_ids.back();
+  m->ctl_max_layer = m->cfg_max_layer = m->exit_ids.back();
   if (const char* e = getenv("DEER_COMPACT")) m->compact = e[0] != '0';
   if (const char* e = getenv("DEER_HEAD_PRE")) m->head_pre = e[0] != '0';
   if (const char* e = getenv("DEER_HEAD_FUSED")) m->head_fused = e[0] != '0';
@@ -1544,7 +1557,7 @@ int deer_model_create(const deer_config* cfg, deer_model** out) {
 }
 
 int deer_model_set_persistent_layer(deer_model* m, int on) {
-  if (m == nullptr) return DEER_ERR_SHAPE;
+  if (m == nullptr || (on && m->env_exit_on)) return DEER_ERR_SHAPE;
   m->persistent_layer = on != 0;  // takes effect for pieces enqueued / captured from now on; one engine per GPU only (see csrc/persistent_layer.hip)
   return DEER_OK;
 }
@@ -1558,7 +1571,7 @@ int deer_model_head_state_changed(deer_model* m) {
 
 // control steps of one environment: the head evaluation as one launch (DEER_HEAD_FUSED=1; off by default: measured slower) or as the eight separate kernels
 int deer_model_set_head_fused(deer_model* m, int on) {
-  if (m == nullptr) return DEER_ERR_SHAPE;
+  if (m == nullptr || (on && m->env_exit_on)) return DEER_ERR_SHAPE;
   m->head_fused = on != 0;   // takes effect for pieces enqueued / captured from now on
   return DEER_OK;
 }
@@ -1689,11 +1702,46 @@ int deer_model_configure_exit(deer_model* m, const int* exit_ids, int n_exit, in
   for (int i = 0; i < n_exit; ++i) ok = ok || exit_ids[i] == cm;
   if (!ok) return DEER_ERR_SHAPE;
   m->exit_ids.assign(exit_ids, exit_ids + n_exit);
-  m->ctl_max_layer = cm;
+  m->ctl_max_layer = m->cfg_max_layer = cm;
   m->thr_type = thr_type;
   m->leq = leq ? 1 : 0;
+  m->env_exit_on = false;                                                     // caps were validated against the old exits
   return DEER_OK;
 }
+
+// per-environment operating points: the same rule as deer_model_configure_exit for every cap (given as the layer index the controller
+// derives, min(max_layer - 1, last exit)); the plan runs to the largest cap
+static int env_exit_set(deer_model* m, const float* rows, int rows_on_device, const int* caps, int n_envs, void* stream) {
+  if (m == nullptr || m->ws == nullptr || rows == nullptr || caps == nullptr || n_envs != m->B) return DEER_ERR_SHAPE;
+  if (m->head_fused || m->persistent_layer) return DEER_ERR_SHAPE;           // the experiments read the shared row only
+  int cmax = -1, eff[DEER_MAX_ENVS];
+  for (int b = 0; b < n_envs; ++b) {
+    eff[b] = std::min(caps[b], m->exit_ids.back());
+    if (std::find(m->exit_ids.begin(), m->exit_ids.end(), eff[b]) == m->exit_ids.end()) return DEER_ERR_SHAPE;
+    cmax = std::max(cmax, eff[b]);
+  }
+  DEER_TRY(deer_env_exit_write(m->Wk<float>(m->env_exit), rows, rows_on_device, eff, n_envs, stream));
+  m->env_exit_on = true;
+  m->ctl_max_layer = cmax;
+  return DEER_OK;
+}
+
+int deer_model_set_env_exit(deer_model* m, const float* rows, const int* caps, int n_envs, void* stream) {
+  return env_exit_set(m, rows, 0, caps, n_envs, stream);
+}
+
+int deer_model_set_env_exit_device(deer_model* m, const float* rows, const int* caps, int n_envs, void* stream) {
+  return env_exit_set(m, rows, 1, caps, n_envs, stream);
+}
+
+int deer_model_clear_env_exit(deer_model* m) {
+  if (m == nullptr) return DEER_ERR_SHAPE;
+  m->env_exit_on = false;
+  m->ctl_max_layer = m->cfg_max_layer;
+  return DEER_OK;
+}
+
+int deer_model_max_layer(const deer_model* m) { return m->ctl_max_layer; }
 
 int deer_model_real_num_exit(const deer_model* m) {
   int n = 0;

@@ -57,15 +57,31 @@ def pack_metrics(results: Sequence[int], exit_layers: Sequence[int], n_layers: i
     return t
 
 
-def reduce_metrics(packed: torch.Tensor, device=None, n_extra: int = 0) -> Dict[str, float]:
-    """all_reduce(SUM) over ranks (a few hundred bytes: latency-bound, xGMI bandwidth is irrelevant) -> metrics of
-    ``print_and_save`` (eval_utils.py:71-118): avg successful length, chain success rates 1-5, avg exit layer (+1)."""
+def _all_reduce_sum(packed: torch.Tensor, device=None) -> torch.Tensor:
     t = packed.clone()
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
         dev = collective_device(device)
         t = t.to(dev) if dev is not None else t
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         t = t.cpu()
+    return t
+
+
+def reduce_metrics(packed: torch.Tensor, device=None, n_extra: int = 0) -> Dict[str, float]:
+    """all_reduce(SUM) over ranks (a few hundred bytes: latency-bound, xGMI bandwidth is irrelevant) -> metrics of
+    ``print_and_save`` (eval_utils.py:71-118): avg successful length, chain success rates 1-5, avg exit layer (+1)."""
+    return _metrics_of(_all_reduce_sum(packed, device), n_extra)
+
+
+def reduce_metrics_points(packed: torch.Tensor, device=None, n_extra: int = 0) -> List[Dict[str, float]]:
+    """The same for k operating points at once: packed (k, n) = one pack_metrics row (+ extras) per point, reduced by ONE all_reduce
+    of the whole matrix (not k collectives); returns k dicts, each what reduce_metrics gives for its row."""
+    assert packed.dim() == 2, packed.shape
+    t = _all_reduce_sum(packed, device)
+    return [_metrics_of(t[p], n_extra) for p in range(t.shape[0])]
+
+
+def _metrics_of(t: torch.Tensor, n_extra: int) -> Dict[str, float]:
     extra = None
     if n_extra:                                                   # caller-defined sums appended to the packed vector
         extra = [float(v) for v in t[-n_extra:]]

@@ -321,6 +321,9 @@ class DeerEngine:
             raise ValueError(f"invalid exit configuration: exit ids {self.exit_ids}, max_layer {self._max_layer_arg} -> the deepest "
                              f"reachable layer {min(self._max_layer_arg - 1, self.exit_ids[-1])} must be one of the exits (otherwise no "
                              "exit check is ever forced; the reference raises KeyError on thresholds[i] there)")
+        if getattr(self, "_env_caps", None) is not None:          # the spine dropped the per-environment table (its caps were checked
+            self._env_caps = self._env_sps = None                 # against the old exits): back to the shared operating point
+            self.ctl_max_layer = min(self._max_layer_arg - 1, self.exit_ids[-1])
 
     def set_compaction(self, on: bool):
         """Env batches: compaction of the rows of exited environments in the trunk (csrc/model.hip; on by default, DEER_COMPACT=0 turns it
@@ -429,6 +432,68 @@ class DeerEngine:
         self._drain_side_streams()                               # a speculative exit check of the last step may still read them
         self.thresholds.copy_(row, non_blocking=True)
 
+    # ------------------------------------------------------------------------------ per-environment operating points
+    def set_env_exit(self, rows, caps: Sequence[int], steps_per_stage: Optional[Sequence[int]] = None):
+        """One exit operating point PER ENVIRONMENT (several exit ratios, DeeR-S and DeeR-B caps or BO candidates side by side in one env
+        batch): environment b compares its deltas with rows[b] and is forced to exit at layer caps[b] (the controller's
+        ``min(max_layer - 1, last exit)``, which must be one of the configured exits).  rows: B sequences of that environment's real
+        thresholds (host), or a (B, 16) float32 CUDA tensor (unused slots 1e8) - an asynchronous update on the current stream.
+        steps_per_stage: per environment (default: the engine's).  exit_ids / threshold type / leq stay shared (configure_exit).
+        The table lives in device memory read at replay: captured graphs survive a change unless the largest cap moves (it bounds
+        the dynamic plan).  ``ExitController._set_threshold_value`` per environment (value_net.py:178-183)."""
+        if self.B == 1:
+            raise NotImplementedError("per-environment operating points need an env batch (n_envs > 1); a one-environment engine has "
+                                      "one operating point (configure_exit / set_thresholds)")
+        if getattr(self.cfg, "layerwise_exit_eval", False):
+            raise NotImplementedError("per-environment operating points with layerwise_exit_eval")
+        caps = [int(c) for c in caps]
+        if len(caps) != self.B:
+            raise ValueError(f"{len(caps)} caps for {self.B} environments")
+        sps = None if steps_per_stage is None else [int(v) for v in steps_per_stage]
+        if sps is not None and (len(sps) != self.B or min(sps) < 1):
+            raise ValueError(f"steps_per_stage must be {self.B} positive ints, got {steps_per_stage}")
+        c_caps = (ctypes.c_int * self.B)(*caps)
+        self._drain_side_streams()                               # a speculative exit check of the last step may still read the table
+        old_max, was_on = self.ctl_max_layer, self.env_caps is not None
+        if isinstance(rows, torch.Tensor) and rows.is_cuda:
+            assert rows.dtype == torch.float32 and tuple(rows.shape) == (self.B, 16) and rows.is_contiguous(), (rows.dtype, rows.shape)
+            rc = self.lib.deer_model_set_env_exit_device(self._h, abi.ptr(rows), c_caps, self.B, _cur_stream())
+        else:
+            rows = [list(r) for r in rows]
+            if len(rows) != self.B or any(len(r) > 16 for r in rows):
+                raise ValueError(f"need {self.B} threshold rows of at most 16 values")
+            t = (ctypes.c_float * (16 * self.B))(*([1e8] * (16 * self.B)))
+            for b, r in enumerate(rows):
+                for k, v in enumerate(r):
+                    t[16 * b + k] = float(v)
+            rc = self.lib.deer_model_set_env_exit(self._h, t, c_caps, self.B, _cur_stream())
+        abi.check(rc, f"deer_model_set_env_exit(caps {caps}; every cap must be one of the exits {self.exit_ids})")
+        self._env_caps, self._env_sps = [min(c, self.exit_ids[-1]) for c in caps], sps
+        self.ctl_max_layer = self.lib.deer_model_max_layer(self._h)
+        # pieces captured on the shared row call the other exit-check entry, and the largest cap bounds the plan: only a change INSIDE
+        # the per-environment mode at the same largest cap keeps them
+        if not was_on or self.ctl_max_layer != old_max:
+            if self._graphs:
+                torch.cuda.synchronize(self.dev)
+            self._drop_graphs()
+
+    def clear_env_exit(self):
+        """Back to the shared operating point (set_thresholds' row, configure_exit's cap and steps_per_stage)."""
+        if getattr(self, "_env_caps", None) is None:
+            return
+        self._drain_side_streams()
+        abi.check(self.lib.deer_model_clear_env_exit(self._h), "deer_model_clear_env_exit")
+        self._env_caps = self._env_sps = None
+        self.ctl_max_layer = self.lib.deer_model_max_layer(self._h)
+        if self._graphs:                                         # the pieces call the per-environment exit-check entry
+            torch.cuda.synchronize(self.dev)
+        self._drop_graphs()
+
+    @property
+    def env_caps(self) -> Optional[List[int]]:
+        """the per-environment caps of set_env_exit, or None (shared operating point)"""
+        return getattr(self, "_env_caps", None)
+
     def reset(self):
         """Episode start: ``clear_all_exit_memory`` + controller state (eval_utils.py:252-277)."""
         # a speculative head evaluation of the last step may still be queued on the side stream; it returns at entry only
@@ -468,7 +533,7 @@ class DeerEngine:
     def dynamic_plan(self):
         """Per layer of the dynamic step: (layer, need_pseudo, is_exit, exit slot).  mosaic_gpt_3b.py:397-443; computed by
         the spine (deer_dynamic_plan)."""
-        key = (tuple(self.exit_ids), self._max_layer_arg)
+        key = (tuple(self.exit_ids), self._max_layer_arg, self.ctl_max_layer)
         if getattr(self, "_plan_key", None) != key:               # on the per-step path: ask the spine once per configuration
             n = self.cfg.n_layers
             a, b, c = (ctypes.c_int * n)(), (ctypes.c_int * n)(), (ctypes.c_int * n)()
@@ -639,10 +704,11 @@ class DeerEngine:
             raise NotImplementedError("dynamic exit with layer 0 in the exit list: the first layer similarity is not implemented "
                                       "(the reference asserts i > 0, value_net.py:119); use exit ids >= 1 or a static exit_id")
         hold = 0                                                  # bit b: environment b is inside a stage (csrc/head.hip: CTL_HOLD per environment)
-        if exit_id is None and self.steps_per_stage != 1:
+        env_sps = getattr(self, "_env_sps", None)                 # set_env_exit: steps_per_stage per environment
+        if exit_id is None and (self.steps_per_stage != 1 or env_sps is not None):
             steps = getattr(self, "_env_steps", None) or [self.cur_step] * self.B
             for b, t in enumerate(steps):
-                if t % self.steps_per_stage != 0:
+                if t % (env_sps[b] if env_sps is not None else self.steps_per_stage) != 0:
                     hold |= 1 << b
         seg_mode = self.segmented and use_graph and sync and exit_id is None and not shadow
         self._seq = (self._seq + 1) & 0xFFFFFF

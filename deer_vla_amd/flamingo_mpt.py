@@ -320,6 +320,9 @@ class MPTFlamingo(nn.Module):
     # ---- forward ---------------------------------------------------------------------------------------------------
     def _sync_controller(self, ctl: ExitController):
         e = self.engine
+        if e.env_caps is not None:                                        # per-environment controllers were in use
+            e.clear_env_exit()
+            self._ctl_sig = None
         sig = (tuple(ctl.exit_id_list), ctl.max_layer, ctl.steps_per_stage, ctl._version, ctl.leq)
         if sig != self._ctl_sig:
             e.configure_exit(ctl.exit_id_list, ctl.max_layer + 1, ctl.steps_per_stage)
@@ -331,6 +334,42 @@ class MPTFlamingo(nn.Module):
                 e.thr_type = abi.THR_TYPES[ctl.value_net.threshold_type]
             self._ctl_sig = sig
         e.cur_step = ctl.cur_step
+
+    def _sync_env_controllers(self, ctls):
+        """One native ExitController PER ENVIRONMENT of the batch (several operating points side by side): exit_id_list, threshold
+        type and leq are shared by the engine (one value net); thresholds, max_layer and steps_per_stage go to the per-environment
+        table (DeerEngine.set_env_exit), which changes without recapturing graphs."""
+        e = self.engine
+        if self.layerwise_exit_eval:
+            raise NotImplementedError("per-environment exit controllers with layerwise_exit_eval (every exit layer acts with its own head)")
+        if e.B == 1:
+            raise NotImplementedError("per-environment exit controllers need an env batch (n_envs > 1)")
+        if len(ctls) != e.B:
+            raise ValueError(f"{len(ctls)} exit controllers for an env batch of {e.B}")
+        c0 = ctls[0]
+        for k, c in enumerate(ctls):
+            if not isinstance(c, ExitController):
+                raise TypeError(f"controller {k}: env batches take the native controller (device-side exit gate), got {type(c).__name__}")
+            if list(c.exit_id_list) != list(c0.exit_id_list):
+                raise ValueError(f"controller {k}: exit_id_list {list(c.exit_id_list)} differs from controller 0's {list(c0.exit_id_list)} "
+                                 "(the exits are shared by the env batch)")
+            if bool(c.leq) != bool(c0.leq):
+                raise ValueError(f"controller {k}: leq={bool(c.leq)} differs from controller 0's leq={bool(c0.leq)} (shared by the env batch)")
+            tt = c.value_net.threshold_type if c.value_net is not None else None
+            tt0 = c0.value_net.threshold_type if c0.value_net is not None else None
+            if tt != tt0:
+                raise ValueError(f"controller {k}: threshold_type {tt!r} differs from controller 0's {tt0!r} (shared by the env batch)")
+            assert c.thresholds is not None, f"controller {k}: please set thresholds before calling forward"
+        shared = ("env", tuple(c0.exit_id_list), bool(c0.leq), tt0)
+        sig = (shared, tuple((c.max_layer, c.steps_per_stage, c._version, id(c)) for c in ctls))
+        if sig != self._ctl_sig:
+            if not (isinstance(self._ctl_sig, tuple) and self._ctl_sig[:1] == (shared,)):
+                e.configure_exit(c0.exit_id_list, c0.exit_id_list[-1] + 1, 1)      # the shared part; clears a previous table
+                e.leq = 1 if c0.leq else 0
+                if tt0 is not None:
+                    e.thr_type = abi.THR_TYPES[tt0]
+            e.set_env_exit([c.threshold_list() for c in ctls], [c.max_layer for c in ctls], [c.steps_per_stage for c in ctls])
+            self._ctl_sig = sig
 
     def _run_llm(self, input_ids, attention_mask, exit_controller, exit_id):
         """Slow host loop (foreign controllers, or a direct ``lang_encoder(...)`` call): vision must already be encoded."""
@@ -370,12 +409,22 @@ class MPTFlamingo(nn.Module):
         (n_envs, ..., 3, S, S), lang_x / attention_mask (n_envs, T) right-padded.  Returns (pose (n_envs, 6), gripper prob (n_envs,),
         exit layers list); ``ensemble``: the mean of every environment's last two exit-check actions instead (eval_utils.py:457-461).  Every environment exits at its own layer on the device; LSTM state per environment.
         ``env_steps``: every environment's step index inside its own sub-task - the per-rollout ``set_timestep(step)`` of the reference
-        (eval_utils.py:662-663) for a controller with ``steps_per_stage`` > 1 (value_net.py:285-286); default: the controller's cur_step."""
+        (eval_utils.py:662-663) for a controller with ``steps_per_stage`` > 1 (value_net.py:285-286); default: the controller's cur_step.
+        ``exit_controller`` may also be a list of n_envs native controllers, one per environment (sharing exit_id_list, threshold type and
+        leq; own thresholds, max_layer and steps_per_stage): one batch then carries several operating points."""
         e = self.engine
-        ctl = getattr(exit_controller, "module", exit_controller)
-        if exit_id is None:
-            assert isinstance(ctl, ExitController), "env batches take the native controller (device-side exit gate)"
-            self._sync_controller(ctl)
+        if isinstance(exit_controller, (list, tuple)):                   # one controller per environment (operating-point sweeps)
+            if exit_id is not None:
+                raise ValueError("exit_id and per-environment exit controllers exclude each other")
+            ctls = [getattr(c, "module", c) for c in exit_controller]
+            self._sync_env_controllers(ctls)
+            if env_steps is None:
+                env_steps = [c.cur_step for c in ctls]
+        else:
+            ctl = getattr(exit_controller, "module", exit_controller)
+            if exit_id is None:
+                assert isinstance(ctl, ExitController), "env batches take the native controller (device-side exit gate)"
+                self._sync_controller(ctl)
         r = e.step(vision_x, vision_gripper, lang_x, attention_mask, exit_id=exit_id, env_steps=env_steps)
         r = r if isinstance(r, list) else [r]
         exits = [x["exit_layer"] for x in r]

@@ -377,7 +377,8 @@ def evaluate_policy_ddp(model: ModelWrapper, env, eval_sequences: Sequence[Tuple
 class BatchedModelWrapper:
     """``ModelWrapper`` for ONE ENV BATCH PER RANK (BASELINE north_star): n_envs environments advance in lock step through one
     control step of the engine; every environment has its own instruction, LSTM history and exit layer.  ``step`` takes the
-    observations / goals of all slots (None for an idle slot) and returns one (7,) float16 action per slot."""
+    observations / goals of all slots (None for an idle slot) and returns one (7,) float16 action per slot.  ``exit_controller`` may
+    be one native controller or a list of n_envs, one per slot (several operating points in one batch: MPTFlamingo.step_env_batch)."""
 
     def __init__(self, model, tokenizer, image_processor, cast_dtype, exit_controller=None, exit_id=None, use_action_ensemble=False):
         m = model.module
@@ -432,8 +433,10 @@ class BatchedModelWrapper:
             self._blank = torch.zeros_like(ref)
         return torch.stack([x if x is not None else self._blank for x in live])
 
-    def step(self, obs_list, goals, env_steps=None):
-        """env_steps: step index of every slot inside its sub-task (idle slots: 0); only read by a controller with steps_per_stage > 1."""
+    def step(self, obs_list, goals, env_steps=None, exit_controller=None):
+        """env_steps: step index of every slot inside its sub-task (idle slots: 0); only read by a controller with steps_per_stage > 1.
+        exit_controller: overrides the wrapper's for this step (evaluate_policy_batched's sweep hands every slot's point here)."""
+        ctl = exit_controller if exit_controller is not None else self.exit_controller
         rgb = self._frames(obs_list, "rgb_static")
         grip = self._frames(obs_list, "rgb_gripper")
         goals = [g if g is not None else "idle" for g in goals]
@@ -447,7 +450,7 @@ class BatchedModelWrapper:
         with torch.no_grad():
             pose, g, exits = self.model.module.step_env_batch(rgb.to(self.cast_type).cuda(non_blocking=True), ids, mask,
                                                               grip.to(self.cast_type).cuda(non_blocking=True),
-                                                              exit_controller=self.exit_controller, exit_id=self.exit_id,
+                                                              exit_controller=ctl, exit_id=self.exit_id,
                                                               ensemble=self.use_action_ensemble, env_steps=env_steps)
         self.current_exit_layers = exits
         A = self.model.module.act_step
@@ -459,8 +462,24 @@ class BatchedModelWrapper:
         return act.to(torch.float16).numpy()
 
 
+def operating_point_log(thresholds: Sequence[float], avg_len: float, avg_exit: float) -> str:
+    """The last three lines the reference's evaluation log ends with for one operating point - comma-separated thresholds, average
+    successful length, average exit layer (+1) - the lines ``bayesian_optimization.get_observation`` reads back (lines[-3:])."""
+    return ",".join(repr(float(t)) for t in thresholds) + "\n" + repr(float(avg_len)) + "\n" + repr(float(avg_exit)) + "\n"
+
+
+def _idle_controller(points):
+    """the controller of a slot with no job during a sweep: exits at its first check (a threshold every delta passes) with the largest
+    cap of the sweep, so the largest cap - the last layer of the engine's plan - stays put and no graph is recaptured"""
+    from .value_net import ExitController
+    top = max(points, key=lambda c: c.max_layer)
+    idle = ExitController(top.value_net, top.exit_id_list, steps_per_stage=1, exit_dist=top.exit_dist, leq=top.leq, max_layer=top.max_layer + 1)
+    idle._set_threshold_value([1e8 if top.leq else -1e8] * idle.real_num_exit)
+    return idle
+
+
 def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_sequences, annotations, task_checker, ep_len: int = EP_LEN,
-                            report: bool = False, groups: Sequence = ()) -> Optional[dict]:
+                            report: bool = False, groups: Sequence = (), operating_points: Optional[Sequence] = None):
     """``evaluate_policy_ddp`` with one env batch per rank: this rank's chains (same slicing, eval_utils.py:523-527) are dealt
     to the n_envs slots, which run them concurrently - per slot exactly the reference's chain / sub-task / step loop
     (eval_utils.py:583-684), per step ONE engine call for all slots.  Metrics reduce like evaluate_policy_ddp.
@@ -468,7 +487,14 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
     ``groups``: further (BatchedModelWrapper, envs) pairs - env batches that run CONCURRENTLY with the first one, each in its own
     host thread on its own stream (build their models with ``MPTFlamingo.sibling()``: same weight arena, own workspace / LSTM state
     / controller).  All groups draw chains from the same queue.  While one batch is in its MFMA-bound vision tower another is in
-    its HBM-bound trunk: four batches of eight reach ~1030 env-steps/s per MI355X against ~900 for one (bench.py `batched_groups`)."""
+    its HBM-bound trunk: four batches of eight reach ~1030 env-steps/s per MI355X against ~900 for one (bench.py `batched_groups`).
+
+    ``operating_points``: k native ExitControllers (shared exit_id_list / threshold type / leq; own thresholds, max_layer,
+    steps_per_stage) - the reference's one-evaluation-per-point loop (eval_ckpts.py over --exit_ratio / --max_layer,
+    bayesian_optimization.py) as ONE run: the jobs are (point, chain) pairs, every chain of this rank runs once per point, a slot
+    that takes a job switches to that point's row and cap (device table, no graph recapture).  Returns a list of k metric dicts (rank
+    0), each what a run with that controller alone reports (``wall_s_mean`` / ``steps_per_s``: the whole sweep's wall time); the
+    metrics of all points reduce in ONE all-reduce."""
     import threading
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
@@ -476,18 +502,24 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
     mine = ddist.shard_sequences(list(eval_sequences), rank, world)
     base = rank * len(mine)
     n_layer = model.model.module.lang_encoder.config.n_layers
-    queue = list(enumerate(mine))
-    results: Dict[int, int] = {}
-    ok_exits, fail_exits, ok_steps = [], [], []
+    points = None if operating_points is None else [getattr(c, "module", c) for c in operating_points]
+    if points is not None and not points:
+        raise ValueError("operating_points: give at least one controller")
+    k = 1 if points is None else len(points)
+    queue = [(p, i, job) for i, job in enumerate(mine) for p in range(k)]      # (point, chain): every chain once per point
+    results: List[Dict[int, int]] = [{} for _ in range(k)]
+    ok_exits, fail_exits, ok_steps = [[] for _ in range(k)], [[] for _ in range(k)], [[] for _ in range(k)]
     lock = threading.Lock()
-    n_steps_box = [0]
+    n_steps_box = [0] * k
     errors = []
+    idle = _idle_controller(points) if points is not None else None
 
     def worker(model, envs):
         B = model.B
         assert len(envs) == B
-        slot = [None] * B                                          # per slot: dict(seq_i, chain, k, step, start, exits, n_ok)
-        n_local = 0
+        slot = [None] * B                                          # per slot: dict(p, seq_i, chain, k, step, start, exits, n_ok)
+        ctls = [idle] * B if points is not None else None          # sweep: the controller of every slot (its job's point)
+        n_local = [0] * k
 
         def start_subtask(b):
             st = slot[b]
@@ -502,24 +534,30 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
                 item = queue.pop(0) if queue else None
             if item is None:
                 slot[b] = None
+                if ctls is not None:
+                    ctls[b] = idle
                 return
-            i, (initial_state, chain) = item
-            slot[b] = dict(seq_i=i, chain=list(chain), k=0, n_ok=0, init=initial_state)
+            p, i, (initial_state, chain) = item
+            slot[b] = dict(p=p, seq_i=i, chain=list(chain), k=0, n_ok=0, init=initial_state)
+            if ctls is not None:
+                ctls[b] = points[p]                                # this slot's row and cap from the next step on
             start_subtask(b)
 
         for b in range(B):
             next_chain(b)
         while any(s is not None for s in slot):
-            if model.exit_controller is not None:                  # eval_utils.py:662-663: every slot's own step index goes with the step
+            if ctls is None and model.exit_controller is not None:  # eval_utils.py:662-663: every slot's own step index goes with the step
                 model.exit_controller.module.set_timestep(0)
             obs = [envs[b].get_obs() if slot[b] is not None else None for b in range(B)]
             acts = model.step(obs, [slot[b]["goal"] if slot[b] is not None else None for b in range(B)],
-                              env_steps=[slot[b]["step"] if slot[b] is not None else 0 for b in range(B)])
+                              env_steps=[slot[b]["step"] if slot[b] is not None else 0 for b in range(B)],
+                              **({} if ctls is None else {"exit_controller": list(ctls)}))
             for b in range(B):
                 st = slot[b]
                 if st is None:
                     continue
-                n_local += 1
+                p = st["p"]
+                n_local[p] += 1
                 st["exits"].append(model.current_exit_layers[b])
                 st["step"] += 1
                 _, _, _, info = envs[b].step(acts[b])
@@ -528,20 +566,21 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
                     if done_ok:
                         st["n_ok"] += 1
                         with lock:
-                            ok_exits.extend(st["exits"])
-                            ok_steps.append(st["step"])
+                            ok_exits[p].extend(st["exits"])
+                            ok_steps[p].append(st["step"])
                         st["k"] += 1
                         if st["k"] < len(st["chain"]):
                             start_subtask(b)
                             continue
                     else:
                         with lock:
-                            fail_exits.extend(st["exits"])
+                            fail_exits[p].extend(st["exits"])
                     with lock:
-                        results[st["seq_i"]] = st["n_ok"]
+                        results[p][st["seq_i"]] = st["n_ok"]
                     next_chain(b)
         with lock:
-            n_steps_box[0] += n_local
+            for p in range(k):
+                n_steps_box[p] += n_local[p]
 
     members = [(model, envs)] + list(groups)
     # every instruction this rank will see must fit the env batch's rows: fail before the run, not in the middle of it
@@ -567,17 +606,21 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
         torch.cuda.synchronize()
         if errors:
             raise errors[0]
-    n_steps_all = n_steps_box[0]
     B = sum(mw.B for mw, _ in members)
     wall = time.perf_counter() - t0
-    res = [results[i] for i in range(len(mine))]
-    packed = ddist.pack_metrics(res, ok_exits, n_layer, wall)
-    extra = torch.tensor([float(n_steps_all)], dtype=torch.float64)
-    out = ddist.reduce_metrics(torch.cat([packed, extra]), n_extra=1)
-    out["n_steps_all"] = int(out.pop("extra")[0])
-    out["wall_s_mean"] = out.pop("llm_time") / world
-    out["steps_per_s"] = out["n_steps_all"] / max(out["wall_s_mean"], 1e-9)
-    out["envs_per_rank"] = B
-    if report and world == 1 and ok_exits:
-        print_and_save(res, ok_exits, fail_exits, ok_steps, [0.0], [0.0], mine, None, n_layer, 0)
-    return out if rank == 0 else None
+    res = [[results[p][i] for i in range(len(mine))] for p in range(k)]
+    packed = torch.stack([torch.cat([ddist.pack_metrics(res[p], ok_exits[p], n_layer, wall),
+                                     torch.tensor([float(n_steps_box[p])], dtype=torch.float64)]) for p in range(k)])
+    outs = ddist.reduce_metrics_points(packed, n_extra=1)        # ONE all-reduce for every point
+    for p, out in enumerate(outs):
+        out["n_steps_all"] = int(out.pop("extra")[0])
+        out["wall_s_mean"] = out.pop("llm_time") / world
+        out["steps_per_s"] = out["n_steps_all"] / max(out["wall_s_mean"], 1e-9)
+        out["envs_per_rank"] = B
+        if report and world == 1 and ok_exits[p]:
+            if points is not None:
+                print(f"Operating point {p} of {k}: max_layer {points[p].max_layer}, thresholds {points[p].threshold_list()}")
+            print_and_save(res[p], ok_exits[p], fail_exits[p], ok_steps[p], [0.0], [0.0], mine, None, n_layer, 0)
+    if rank != 0:
+        return None
+    return outs if points is not None else outs[0]

@@ -196,6 +196,28 @@ class ExitController:
         return self
 
 
+def controllers_from_values(value_net: Optional[ActionValueNet], exit_id_list: Sequence[int], values: torch.Tensor,
+                            exit_ratios: Sequence[float], max_layers=None, steps_per_stage: int = 1, exit_dist: str = "exp",
+                            leq: bool = True, model_name: str = "mpt_dolly_3b") -> List[ExitController]:
+    """k operating points from ONE calibration: the ``values=`` branch of ``set_threshold`` (value_net.py:185-264) solved once per point
+    on the same (n_exit, n_sample) value matrix.  max_layers: None (every exit reachable), one int for all points, or one per exit ratio
+    (the reference's ``--max_layer``: DeeR-S vs DeeR-B).  Returns one ExitController per point, in order - a list that
+    ``MPTFlamingo.step_env_batch`` / ``evaluate_policy_batched(operating_points=...)`` take."""
+    ratios = [float(r) for r in exit_ratios]
+    if max_layers is None or isinstance(max_layers, int):
+        caps = [max_layers if max_layers is not None else list(exit_id_list)[-1] + 1] * len(ratios)
+    else:
+        caps = [int(m) for m in max_layers]
+        if len(caps) != len(ratios):
+            raise ValueError(f"{len(caps)} max_layer values for {len(ratios)} exit ratios (pass one per point)")
+    out = []
+    for r, cap in zip(ratios, caps):
+        c = ExitController(value_net, exit_id_list, steps_per_stage=steps_per_stage, exit_dist=exit_dist, leq=leq, max_layer=cap)
+        c.set_threshold_from_values(values, r, model_name)
+        out.append(c)
+    return out
+
+
 def generate_action_values(args, model, value_net: ActionValueNet, calvin_loader, device_id=None, generator=None):
     """value_net.py:301-397 on the native engine.  ``calvin_loader`` yields the reference's CALVIN batches:
     ``batch[0]`` images (bs, W, 3, S, S), ``batch[1]`` = (input_ids (bs, T), attention_mask (bs, T)), ``batch[3]`` gripper

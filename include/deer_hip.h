@@ -394,6 +394,18 @@ int deer_head_final_multi(const float* src, int src_stride, int in_dim, int pro,
                           int layer, int slot, const float* thresholds, int force, int thr_type, int leq, const float* h_tmp,
                           const float* c_tmp, float* h_state, float* c_state, int L, int H, int B, float* action_dbg, float eps,
                           int w_is_f32, int multi_step_action, float* act_ext, void* stream);
+/* the same with a per-environment operating point (several exit ratios / layer caps side by side in one env batch): env_exit is the table
+ * [DEER_MAX_ENVS * 16 + DEER_MAX_ENVS] words of csrc/common.h (ENV_EXIT_*): f32 threshold row of environment b at b * 16, int32 layer cap of
+ * environment b at word 256 + b.  Environment b's check compares with its own row and is forced at layer >= its cap (or when `force` is
+ * set); everything else is deer_head_final_multi's. */
+int deer_head_final_env(const float* src, int src_stride, int in_dim, int pro, const float* lnw0, const float* lnb0, const float* lnw1,
+                        const float* lnb1, const void* Wa, const float* ba, const void* Wg, const float* bg, int* ctl, int kind,
+                        int layer, int slot, const float* env_exit, int force, int thr_type, int leq, const float* h_tmp,
+                        const float* c_tmp, float* h_state, float* c_state, int L, int H, int B, float* action_dbg, float eps,
+                        int w_is_f32, int multi_step_action, float* act_ext, void* stream);
+/* writes n_envs rows (f32 [n_envs][16], device memory when rows_on_device, else host memory copied into the launch) and n_envs caps (host
+ * int32) into an env_exit table, as one launch on `stream`. */
+int deer_env_exit_write(float* env_exit, const float* rows, int rows_on_device, const int* caps, int n_envs, void* stream);
 /* ---- one head evaluation as ONE launch (csrc/head.hip: head_fused_kernel; replaces the eight launches above on control steps of one
  * environment: pool -> L <= 4 LSTM layers (recurrent half from deer_head_lstm_hh) -> <= 3 hidden Linears -> output Linear + exit gate).
  * G workgroups stay resident; the vectors between the phases travel as data-tagged 8-byte granules (relaxed agent-scope atomics), the

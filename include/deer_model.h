@@ -85,7 +85,7 @@ int deer_model_knows_tensor(const deer_model* m, const char* name);             
 int deer_model_missing_tensors(const deer_model* m, char* buf, int buflen);      /* host only: count of REQUIRED tensors not loaded; names (newline separated) into buf */
 /* host only: location of a named buffer (bytes from the base).  which = 0 arena, 1 workspace.  Workspace names: "img", "vx",
  * "vis_x", "vis_x_f32", "kv_all", "ids", "key_mask", "text_time", "x", "hidden", "h_state", "c_state", "h_tmp", "c_tmp",
- * "h_shadow", "c_shadow", "pooled", "ctl", "thresholds", "step_info", "action_dbg" ([n_envs][64]: pose 6 A | gripper A | logit A),
+ * "h_shadow", "c_shadow", "pooled", "ctl", "thresholds", "env_exit", "step_info", "action_dbg" ([n_envs][64]: pose 6 A | gripper A | logit A),
  * "act_ext" (multi_step_action > 1: [n_envs][4][64] previous / committed / ensemble action), "lw_state" (layerwise_exit_eval). */
 int deer_model_buffer(const deer_model* m, int which, const char* name, long* offset, long* bytes);
 
@@ -103,6 +103,19 @@ int deer_model_set_head_fused(deer_model* m, int on);
 int deer_model_set_persistent_layer(deer_model* m, int on);
 int deer_model_configure_exit(deer_model* m, const int* exit_ids, int n_exit, int max_layer, int thr_type, int leq);
 int deer_model_real_num_exit(const deer_model* m);
+/* Per-environment operating points (one env batch carrying several exit ratios / DeeR-S and DeeR-B caps side by side).  rows: f32
+ * [n_envs][16] threshold rows (unused slots 1e8, like "thresholds"), host memory (deer_model_set_env_exit) or device memory
+ * (deer_model_set_env_exit_device: an asynchronous update between steps); caps: host int32 [n_envs], environment b's deepest exit layer
+ * (the controller's min(max_layer - 1, last exit); a cap beyond the last exit means the last exit): each must then be one of the
+ * configured exits, else DEER_ERR_SHAPE (deer_model_configure_exit's rule).  n_envs must be the
+ * model's.  The table is written by one launch on `stream` and read by every exit check at replay: captured pieces stay valid as long as
+ * the largest cap (the plan's last layer, deer_model_max_layer) does not change.  DEER_ERR_SHAPE while the one-launch head evaluation or the
+ * persistent trunk layer is on (both know the shared row only; they refuse to be switched on while a table is active).
+ * deer_model_clear_env_exit returns to the shared row and the configured cap; deer_model_configure_exit clears the table too. */
+int deer_model_set_env_exit(deer_model* m, const float* rows, const int* caps, int n_envs, void* stream);
+int deer_model_set_env_exit_device(deer_model* m, const float* rows, const int* caps, int n_envs, void* stream);
+int deer_model_clear_env_exit(deer_model* m);
+int deer_model_max_layer(const deer_model* m);      /* the deepest exit layer of the dynamic plan (the largest cap while a table is active) */
 
 /* ---- the three coarse operators of SURVEY.md §8b ------------------------------------------------------------------ */
 /* images: bf16 [n_images,3,S,S] (already CLIP-normalised); tokens_out: f32 [n_images,256,W] patch tokens (x[:,1:], no ln_post)
