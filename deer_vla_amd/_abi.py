@@ -148,6 +148,14 @@ SIGNATURES = {
     "deer_head_eval_layerwise": [P, I, I, I, I, P],
     "deer_step_enqueue": [P, I, I, I, I, P, P],
     "deer_dynamic_plan": [P, P, P, P, I],
+    # window mode of the head (csrc/head_seq.hip, include/deer_model.h deer_head_sequence)
+    "deer_head_seq_pool": [P, P, P, I, I, I, I, P],
+    "deer_head_seq_state_u": [P, P, P, P, P, I, I, P],
+    "deer_head_seq_gemm": [P, L, P, I, P, P, L, I, I, I, I, P],
+    "deer_head_seq_lstm_step": [P, L, P, L, P, I, P, P, P, L, P, P, I, I, P],
+    "deer_head_seq_ln": [P, L, P, L, P, P, I, I, F, I, P],
+    "deer_head_sequence": [P, I, P, I, I, I, P, P, P, I, P, P, P, P],
+    "deer_head_sequence_ex": [P, I, P, I, I, I, P, P, P, I, P, P, P, P, P, P],
     "deer_model_n_chains": [P],
     "deer_prof_enable": [P, I],
     "deer_prof_count": [P],
@@ -170,6 +178,7 @@ A_BF16, A_SLABS_GELU, A_SLABS, A_F32 = 0, 1, 2, 3
 X_RAW, X_POOL_MAX, X_POOL_AVG, X_LN = 0, 1, 2, 3
 PRO_RAW, PRO_LN, PRO_GROUP_LN_RELU, PRO_GROUP_RELU = 0, 1, 2, 3
 KIND_PSEUDO, KIND_CHECK, KIND_COMMIT = 0, 1, 2
+SEQ_LAST_ACTION, SEQ_STATE = 1, 2                 # deer_head_sequence flags
 THR_TYPES = {"L2": 0, "mean": 1, "max": 2, "cosine": 3}
 
 _lib = None

@@ -3,7 +3,8 @@ engine's head kernels (csrc/head.hip).
 
 Only the inference behaviour DeeR uses is mirrored: max/avg pooling over the text tokens (:519-520), the 4-layer
 (LayerNorm-)LSTM evaluated one time step at a time with the ``update_hidden_state`` commit/stash protocol
-(:548-558) and the two MLP heads (:604-605).  The weights live in the engine (``DeerEngine.head``); this object is the
+(:548-558) and the two MLP heads (:604-605).  Window mode - a batch of feature sequences, (bs, L, T, d) or (bs * window_size, T, d)
+(:509-518,588-597) - runs the whole sequences in one spine call (DeerEngine.head_sequence, csrc/head_seq.hip).  The weights live in the engine (``DeerEngine.head``); this object is the
 stateful handle the reference's harness and ``ActionValueNet`` poke at: ``hidden_state``, ``history_memory``,
 ``window_size``, ``clear_hidden_state()``, ``update_hidden_state()``, ``__call__(feat, update_hidden_state=...)``.
 
@@ -29,9 +30,14 @@ class DeterministicDecoder:
         self.is_extra_exit = True
 
     # ---- state (kept on the device inside the engine) -------------------------------------------------------
+    # A window call over bs sequences leaves h_n as the hidden state (action_head.py:592).  bs == n_envs: it becomes the engine's committed
+    # LSTM state, so a following step call continues from it; otherwise it is held here (engine._window_hidden) and a step call raises
+    # until clear_hidden_state() / engine.reset(), as the reference's LSTM fails on the batch mismatch.
     @property
     def hidden_state(self):
         e = self.engine
+        if getattr(e, "_window_hidden", None) is not None:
+            return e._window_hidden
         if not bool(e.h_state.any()) and not bool(e.c_state.any()):
             return None
         return (e.h_state.clone(), e.c_state.clone())           # (L, 1, H) like the reference (action_head.py:61-63)
@@ -39,6 +45,10 @@ class DeterministicDecoder:
     @hidden_state.setter
     def hidden_state(self, value):
         e = self.engine
+        e._window_hidden = None
+        if value is not None and value[0].numel() != e.h_state.numel():
+            e._window_hidden = (value[0], value[1])
+            return
         if value is None:
             e.h_state.zero_()
             e.c_state.zero_()
@@ -64,7 +74,10 @@ class DeterministicDecoder:
                  update_hidden_state: bool = True):
         e = self.engine
         if input_feature.dim() != 3 or input_feature.shape[0] != 1:
-            raise NotImplementedError("native head: step mode only, input (1, T, d) (window mode is a 'next' row, SURVEY §8f.1)")
+            return self._window(input_feature, h_0, state_tensor, return_feature, return_aggregate_feature, with_gripper_logits)
+        if getattr(e, "_window_hidden", None) is not None:
+            raise RuntimeError(f"the hidden state holds {e._window_hidden[0].shape[1]} sequences from a window call, the step mode runs "
+                               f"{e.B}: call clear_hidden_state() (or reset the engine) first")
         T = input_feature.shape[1]
         feats = input_feature.reshape(T, -1).to(device=e.dev, dtype=torch.float32).contiguous()
         self.history_memory.append(None)                      # the reference appends the pooled feature (unbounded leak)
@@ -86,3 +99,48 @@ class DeterministicDecoder:
             pooled = feats.amax(0, keepdim=True) if e.cfg.pooling == "max" else feats.mean(0, keepdim=True)
             return pose, grip, pooled
         return pose, grip
+
+    def _window(self, input_feature, h_0, state_tensor, return_feature, return_aggregate_feature, with_gripper_logits):
+        """Window mode (action_head.py:509-518 reshape rules, :588-597): the LSTM runs along each sequence from h_0 or zero."""
+        e = self.engine
+        x = input_feature
+        if x.dim() == 4:                                     # (bs, L, T, d): the window size of this call
+            cur_ws = int(x.shape[1])
+            x = x.reshape(-1, *x.shape[2:])
+        else:                                                # (bs * window_size, T, d)
+            cur_ws = int(self.window_size)
+        if x.dim() != 3:
+            raise ValueError(f"DeterministicDecoder: input must be (1, T, d), (bs, L, T, d) or (bs * window_size, T, d), got {tuple(input_feature.shape)}")
+        rows, T, d = (int(v) for v in x.shape)
+        if cur_ws < 1 or rows % cur_ws:
+            raise ValueError(f"DeterministicDecoder: {rows} feature rows are not whole windows of window_size {cur_ws}")
+        N = rows // cur_ws
+        if cur_ws == 1:                                      # one step per sequence: the reference's step mode (:548)
+            if N == 1:
+                return self(x, h_0, state_tensor, return_feature, return_aggregate_feature, with_gripper_logits)
+            raise NotImplementedError(f"native head: step mode runs one sequence per call here ({N} given with window size 1)")
+        h0 = c0 = None
+        if h_0 is not None:                                  # nn.LSTM's (h_0, c_0)
+            h0, c0 = h_0
+        st = None
+        if getattr(e.cfg, "use_state", False):
+            if state_tensor is None:
+                raise ValueError("a use_state head needs state_tensor (bs, L, 15) or (bs * L, 15) in window mode (action_head.py:524-536)")
+            st = state_tensor
+        from .ops import head_sequence_shapes
+        head_sequence_shapes(e.cfg, (N, cur_ws, T, d), h0, c0, st, self.last_action)   # every shape checked before the device is touched
+        feats = x.reshape(N, cur_ws, T, d)
+        actions, h_n, c_n, org_feat, agg = e.head_sequence(feats, h0, c0, st, head=getattr(self, "head", 0), last_action=self.last_action,
+                                                           features=True)
+        self.hidden_state = (h_n, c_n)                       # :592 (the engine's committed state when bs == n_envs)
+        A = e.A
+        pose = actions[..., :6 * A]
+        grip = actions[..., 6 * A:7 * A]
+        gripper = (grip, actions[..., 7 * A:8 * A]) if with_gripper_logits else grip
+        if return_aggregate_feature:
+            return pose, gripper, agg
+        if return_feature:
+            if org_feat.shape[1] == 1:                       # :539-543
+                org_feat = org_feat.view(cur_ws, org_feat.shape[-1])
+            return pose, gripper, org_feat
+        return pose, gripper

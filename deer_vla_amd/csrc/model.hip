@@ -214,6 +214,8 @@ struct deer_model {
   bool env_exit_on = false;         // deer_model_set_env_exit*: exit checks read env_exit; ctl_max_layer = the largest cap
   bool persistent_layer = false;    // N1 experiment: one launch per trunk layer (DEER_PERSISTENT_LAYER=1 / deer_model_set_persistent_layer)
   size_t ghh = 0;
+  void* seq_scratch = nullptr;      // deer_head_sequence: device scratch of the window-mode head, allocated at first use and grown on demand
+  size_t seq_bytes = 0;
   bool head_pre = true;             // recurrent half of the LSTM head once per control step (DEER_HEAD_PRE=0: every evaluation streams W_hh again)
   bool ghh_valid = false;           // the pre-pass result matches h_state: set by deer_begin_step, cleared by deer_model_head_state_changed
   bool compact = true;              // env batches: compaction of exited environments (DEER_COMPACT=0 / deer_model_set_compaction)
@@ -1585,6 +1587,7 @@ int deer_model_set_compaction(deer_model* m, int on) {
 void deer_model_destroy(deer_model* m) {
   if (m == nullptr) return;
   for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
+  if (m->seq_scratch != nullptr) (void)hipFree(m->seq_scratch);
   delete m;
 }
 
@@ -1821,6 +1824,138 @@ int deer_model_layerwise_head(const deer_model* m, int layer) {
 int deer_head_eval_layerwise(deer_model* m, int head, int layer, int T, int use_mask, void* stream) {
   if (m->ws == nullptr || head < 1 || head > (int)m->lw.size() || layer < 0 || layer >= m->c.n_layers || T <= 0) return DEER_ERR_SHAPE;
   return head_eval(m, layer, T, DEER_KIND_COMMIT, -1, false, false, false, true, nullptr, use_mask != 0, stream, head);
+}
+
+// ---- window mode of the head (DeterministicDecoder.forward on sequences, action_head.py:499-611) -----------------------------------------
+// Layer-major schedule of csrc/head_seq.hip over chunks of Nc sequences (Nc L <= kSeqRows rows, whole sequences per chunk):
+// pool (+ state embedding) -> per LSTM layer: [LayerNorm of the previous layer's outputs] -> W_ih projection of all rows -> L recurrent
+// steps -> [LayerNorm] -> hidden Linears of both MLP heads -> output Linears (tanh | sigmoid + logit) straight into `actions`.
+constexpr long kSeqRows = 2048;
+
+int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, int L, int T, const float* h0, const float* c0, const float* state,
+                          int flags, float* actions, float* h_n, float* c_n, float* feat_out, float* agg_out, void* stream) {
+  const deer_config& c = m->c;
+  const bool last = (flags & DEER_SEQ_LAST_ACTION) != 0, with_state = (flags & DEER_SEQ_STATE) != 0;
+  if (m->arena == nullptr || feats == nullptr || actions == nullptr || N <= 0 || L <= 0 || T <= 0 || (flags & ~3) || head < 0 ||
+      head > (int)m->lw.size() || (h0 == nullptr) != (c0 == nullptr) || (h_n == nullptr) != (c_n == nullptr))
+    return DEER_ERR_SHAPE;
+  // use_state: the state rows are required, and only extra_exit carries the state embedding (action_head.py:443-453)
+  if ((bool)c.use_state != with_state || (with_state && (state == nullptr || head != 0))) return DEER_ERR_SHAPE;
+  const HeadW* hw = head > 0 ? &m->lw[head - 1] : nullptr;
+  const std::vector<LstmW>& lstm_w = hw ? hw->lstm : m->lstm;
+  const std::vector<FcW>& fc_w = hw ? hw->fc : m->fc;
+  const size_t wa = hw ? hw->wa : m->wa, ba = hw ? hw->ba : m->ba, wg = hw ? hw->wg : m->wg, bg = hw ? hw->bg : m->bg;
+  const int d = m->d, H = m->H, Lh = m->Lh, A = std::max(1, c.multi_step_action), wk = m->wkind;
+  const int fc_max = m->n_fc > 0 ? m->fc_dims[0] : H;
+  // chunk: whole sequences, at most kSeqRows rows (a longer sequence is a chunk of its own)
+  const int Nc = (int)std::max(1L, std::min((long)N, kSeqRows / L));
+  const long R = (long)Nc * L;
+  // scratch (floats): X [R][max(d, H)], u [R][2d] + emb [R][d] (use_state), pre [R][4H], y [R][H], c [Nc][H], zero h [Nc][H],
+  // two MLP buffers per head [R][fc_max]
+  const long xw = std::max(d, H);
+  const long n_x = R * xw, n_u = with_state ? R * 2 * d : 0, n_emb = with_state ? R * d : 0, n_pre = R * 4 * H, n_y = R * H,
+             n_c = (long)Nc * H, n_z = R * fc_max;
+  const size_t need = (size_t)(n_x + n_u + n_emb + n_pre + n_y + 2 * n_c + 4 * n_z) * sizeof(float) + 16 * 256;
+  if (need > m->seq_bytes) {                            // host only: the first call (or a larger one) allocates
+    if (m->seq_scratch != nullptr) {
+      if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return DEER_ERR_LAUNCH;
+      (void)hipFree(m->seq_scratch);
+      m->seq_scratch = nullptr;
+      m->seq_bytes = 0;
+    }
+    if (hipMalloc(&m->seq_scratch, need) != hipSuccess) return DEER_ERR_LAUNCH;
+    m->seq_bytes = need;
+  }
+  char* base = reinterpret_cast<char*>(m->seq_scratch);
+  size_t off = 0;
+  auto take = [&](long n) { float* p = reinterpret_cast<float*>(base + off); off += ((size_t)n * sizeof(float) + 255) & ~size_t(255); return p; };
+  float* X = take(n_x);
+  float* U = with_state ? take(n_u) : nullptr;
+  float* EMB = with_state ? take(n_emb) : nullptr;
+  float* PRE = take(n_pre);
+  float* Y = take(n_y);
+  float* CS = take(n_c);
+  float* HZ = take(n_c);
+  float* Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
+  hipStream_t st = (hipStream_t)stream;
+  if (hipMemsetAsync(HZ, 0, (size_t)n_c * sizeof(float), st) != hipSuccess) return DEER_ERR_LAUNCH;
+  const int out_rows_per = last ? 1 : L;
+  for (int n0 = 0; n0 < N; n0 += Nc) {
+    const int nc = std::min(Nc, N - n0);
+    const long rows = (long)nc * L;
+    // ---- pool (+ robot-state embedding, action_head.py:524-536) ----
+    if (with_state) {
+      const float* sp = state + (long)n0 * L * 8;
+      DEER_TRY(deer_head_seq_state_u(sp, m->A<float>(m->w_arm), m->A<float>(m->b_arm), m->A<float>(m->e_grip), U, (int)rows, d, stream));
+      DEER_TRY(deer_head_seq_gemm(U, 2 * d, m->A<void>(m->w_state), wk, m->A<float>(m->b_state), EMB, d, (int)rows, d, 2 * d, DEER_SEQ_EPI_NONE, stream));
+    }
+    DEER_TRY(deer_head_seq_pool(feats + (long)n0 * L * T * d, EMB, X, (int)rows, T, d, c.pooling_avg, stream));
+    if (feat_out != nullptr &&
+        hipMemcpyAsync(feat_out + (long)n0 * L * d, X, (size_t)rows * d * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return DEER_ERR_LAUNCH;
+    // ---- the LSTM, layer by layer ----
+    for (int l = 0; l < Lh; ++l) {
+      const LstmW& Lw = lstm_w[l];
+      const float* xin = X;
+      int in_dim = d;
+      if (l > 0) {
+        in_dim = H;
+        if (c.lstm_layernorm) DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(lstm_w[l - 1].lnw), m->A<float>(lstm_w[l - 1].lnb), (int)rows, H, kEps, 0, stream));
+        else xin = Y;
+      }
+      DEER_TRY(deer_head_seq_gemm(xin, in_dim, m->A<void>(Lw.wih), wk, m->A<float>(Lw.bih), PRE, 4L * H, (int)rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+      const long so = (long)l * N * H + (long)n0 * H;             // (L_lstm, N, H) state tensors
+      if (c0 != nullptr) {
+        if (hipMemcpyAsync(CS, c0 + so, (size_t)nc * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return DEER_ERR_LAUNCH;
+      } else if (hipMemsetAsync(CS, 0, (size_t)nc * H * sizeof(float), st) != hipSuccess) {
+        return DEER_ERR_LAUNCH;
+      }
+      for (int t = 0; t < L; ++t) {
+        const float* hp = t > 0 ? Y + (long)(t - 1) * H : (h0 != nullptr ? h0 + so : HZ);
+        const long ldh = t > 0 ? (long)L * H : H;
+        const bool fin = t == L - 1 && h_n != nullptr;
+        DEER_TRY(deer_head_seq_lstm_step(PRE + (long)t * 4 * H, (long)L * 4 * H, hp, ldh, m->A<void>(Lw.whh), wk, m->A<float>(Lw.bhh), CS,
+                                         Y + (long)t * H, (long)L * H, fin ? h_n + so : nullptr, fin ? c_n + so : nullptr, nc, H, stream));
+      }
+    }
+    // ---- LSTM output x (LayerNorm'ed with lstm_layernorm), all steps or the last one (last_action, :596-597) ----
+    const float* xo = Y;
+    if (c.lstm_layernorm) {
+      DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(lstm_w.back().lnw), m->A<float>(lstm_w.back().lnb), (int)rows, H, kEps, 0, stream));
+      xo = X;
+    }
+    const float* x_rows = last ? xo + (long)(L - 1) * H : xo;
+    const long ld_x = last ? (long)L * H : H;
+    const int mr = last ? nc : (int)rows;
+    if (agg_out != nullptr &&
+        hipMemcpy2DAsync(agg_out + (long)n0 * out_rows_per * H, H * sizeof(float), x_rows, ld_x * sizeof(float), H * sizeof(float), mr,
+                         hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return DEER_ERR_LAUNCH;
+    // ---- the two MLP heads (action_head.py:86-136), outputs [pose 6A | gripper prob A | logit A] per row ----
+    float* act = actions + (long)n0 * out_rows_per * 8 * A;
+    for (int g = 0; g < 2; ++g) {
+      const float* src = x_rows;
+      long lds = ld_x;
+      int kin = H;
+      for (int fi = 0; fi < m->n_fc; ++fi) {
+        const FcW& F = fc_w[fi];
+        const int dim = m->fc_dims[fi];
+        float* z = Z[g][fi & 1];
+        DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(F.w[g]), wk, m->A<float>(F.b[g]), z, dim, mr, dim, kin,
+                                    c.mlp_layernorm ? DEER_SEQ_EPI_NONE : DEER_SEQ_EPI_RELU, stream));
+        if (c.mlp_layernorm) DEER_TRY(deer_head_seq_ln(z, dim, z, dim, m->A<float>(F.lnw[g]), m->A<float>(F.lnb[g]), mr, dim, kEps, 1, stream));
+        src = z; lds = dim; kin = dim;
+      }
+      if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wa), wk, m->A<float>(ba), act, 8L * A, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
+      else DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wg), wk, m->A<float>(bg), act + 6 * A, 8L * A, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
+    }
+  }
+  return DEER_OK;
+}
+
+int deer_head_sequence(deer_model* m, int head, const float* feats, int N, int L, int T, const float* h0, const float* c0, const float* state,
+                       int flags, float* actions, float* h_n, float* c_n, void* stream) {
+  return deer_head_sequence_ex(m, head, feats, N, L, T, h0, c0, state, flags, actions, h_n, c_n, nullptr, nullptr, stream);
 }
 
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream) {

@@ -507,6 +507,7 @@ class DeerEngine:
         self.ctl.zero_()
         self._shadow_on = False
         self.cur_step = 0
+        self._window_hidden = None                                  # DeterministicDecoder: h_n of a window call over another batch size
 
     def reset_env(self, b: int):
         """Episode start of ONE environment of the batch (its sub-task changed): clears its LSTM state and control block; the
@@ -1111,6 +1112,18 @@ class DeerEngine:
             self.c_state.copy_(self.c_tmp)
             self._head_state_changed()
         return self.action_dbg.clone()
+
+    def head_sequence(self, feats: torch.Tensor, h0: Optional[torch.Tensor] = None, c0: Optional[torch.Tensor] = None,
+                      state: Optional[torch.Tensor] = None, head: int = 0, last_action: bool = False, features: bool = False):
+        """The head's window mode (DeterministicDecoder.forward on sequences, action_head.py:499-611) as ONE spine call
+        (include/deer_model.h deer_head_sequence, csrc/head_seq.hip): feats (N, L, T, d) -> (actions (N, L or 1, 8 A) [pose 6 A |
+        gripper prob A | logit A], h_n, c_n (L_lstm, N, H)) on the device, the LSTM run from (h0, c0) or from zero.  Any N (chunked inside
+        the spine); head 0 = extra_exit, k >= 1 = per-layer head k (layerwise_exit_eval); state: robot_obs rows of a use_state model.
+        features=True also returns the pooled (+ state) features (N, L, d) and the LSTM output (N, L or 1, H).  The engine's committed
+        LSTM state does not change."""
+        from .ops import run_head_sequence
+        f = feats.to(device=self.dev)
+        return run_head_sequence(self.lib, self._h, self.cfg, f, h0, c0, state, head, last_action, features)
 
     def generate_values(self, hidden: torch.Tensor, rand_layers, threshold_type: str = "L2", group: int = 8) -> torch.Tensor:
         """``ActionValueNet.forward(mode='generate')`` (value_net.py:134-160): for the time steps seq_id in [W/2-1, W-1) the action of

@@ -7,6 +7,9 @@ through PyTorch-ROCm custom ops").  These are the three coarse operators SURVEY.
   deer::llm_early_exit(Tensor ids, Tensor? key_mask, Tensor media, int model, int exit_id, bool shadow)
                                         -> (Tensor ctl, Tensor hidden)        mosaic_gpt_3b.py:274-449 + value_net.py:277-297
                                                                                + action_head.py:499-611 (exit gate on the device)
+  deer::action_head_sequence(Tensor feats, Tensor? h0, Tensor? c0, int model, int head, bool last_action, Tensor? state=None)
+                                        -> (Tensor actions, Tensor h_n, Tensor c_n) DeterministicDecoder.forward on sequences
+                                                                               (action_head.py:499-611, window mode :588-595)
 
 ``model`` is the address of a ``deer_model`` (``NativeModel.handle``): weights, workspace, LSTM state and the exit controller
 configuration live in that object, like they live in the reference's stateful ``MPTFlamingo`` module.
@@ -167,6 +170,74 @@ def _(ids, key_mask, media, model, exit_id, shadow):
     T = ids.reshape(m.B, -1).shape[1]
     return (ids.new_empty((m.B, abi.CTL_WORDS), dtype=torch.int32),
             media.new_empty((m.cfg.n_layers, m.B * T, m.cfg.d_model), dtype=torch.float32))
+
+
+def head_sequence_shapes(cfg, feats_shape, h0=None, c0=None, state=None, last_action: bool = False):
+    """Host-side checks of a window-mode head call (no device touched): feats (N, L, T, d), h0 / c0 (L_lstm, N, H) or None, state
+    (N, L, S) / (N * L, S) robot_obs rows (use_state models only).  Returns (N, L, T, shapes of actions, h_n / c_n)."""
+    if len(feats_shape) != 4:
+        raise ValueError(f"head sequence: feats must be (N, L, T, d), got {tuple(feats_shape)}")
+    N, L, T, d = (int(v) for v in feats_shape)
+    if min(N, L, T) < 1 or d != cfg.d_model:
+        raise ValueError(f"head sequence: feats (N, L, T, d) = {tuple(feats_shape)} for d_model {cfg.d_model}")
+    Lh, H, A = cfg.lstm_num_layers, cfg.head_hidden, max(1, int(getattr(cfg, "multi_step_action", 1)))
+    if (h0 is None) != (c0 is None):
+        raise ValueError("head sequence: h0 and c0 come together (nn.LSTM's (h_0, c_0)) or not at all")
+    for t in (h0, c0):
+        if t is not None and tuple(t.shape) != (Lh, N, H):
+            raise ValueError(f"head sequence: initial state must be {(Lh, N, H)}, got {tuple(t.shape)}")
+    if getattr(cfg, "use_state", False):
+        if state is None:
+            raise ValueError("head sequence: a use_state head needs the robot state of every step (state_tensor, action_head.py:524-536)")
+        if state.numel() % (N * L) or state.numel() // (N * L) < 7:
+            raise ValueError(f"head sequence: state {tuple(state.shape)} does not hold one robot_obs row per (sequence, step) of {N} x {L}")
+    elif state is not None:
+        raise ValueError("head sequence: state given to a head without use_state")
+    return N, L, T, (N, 1 if last_action else L, 8 * A), (Lh, N, H)
+
+
+def run_head_sequence(lib, handle, cfg, feats: torch.Tensor, h0=None, c0=None, state=None, head: int = 0, last_action: bool = False,
+                      features: bool = False):
+    """One ``deer_head_sequence_ex`` call on the current stream: (actions (N, L or 1, 8 A), h_n, c_n[, pooled (N, L, d), lstm_out (N, L or 1, H)])."""
+    N, L, T, a_shape, s_shape = head_sequence_shapes(cfg, feats.shape, h0, c0, state, last_action)
+    dev = feats.device
+    f = feats.to(torch.float32).contiguous()
+    h0c = h0.to(device=dev, dtype=torch.float32).contiguous() if h0 is not None else None
+    c0c = c0.to(device=dev, dtype=torch.float32).contiguous() if c0 is not None else None
+    st = None
+    flags = abi.SEQ_LAST_ACTION if last_action else 0
+    if state is not None:                       # (arm pose robot_obs[:6], gripper robot_obs[-1], pad) per row, like "state_in"
+        s2 = state.reshape(N * L, -1).to(device=dev, dtype=torch.float32)
+        st = torch.zeros(N * L, 8, dtype=torch.float32, device=dev)
+        st[:, :6] = s2[:, :6]
+        st[:, 6] = s2[:, -1]
+        flags |= abi.SEQ_STATE
+    actions = torch.empty(a_shape, dtype=torch.float32, device=dev)
+    h_n = torch.empty(s_shape, dtype=torch.float32, device=dev)
+    c_n = torch.empty(s_shape, dtype=torch.float32, device=dev)
+    fo = torch.empty(N, L, cfg.d_model, dtype=torch.float32, device=dev) if features else None
+    ao = torch.empty(N, a_shape[1], cfg.head_hidden, dtype=torch.float32, device=dev) if features else None
+    abi.check(lib.deer_head_sequence_ex(handle, int(head), abi.ptr(f), N, L, T, abi.ptr(h0c), abi.ptr(c0c), abi.ptr(st), flags, abi.ptr(actions),
+                                        abi.ptr(h_n), abi.ptr(c_n), abi.ptr(fo), abi.ptr(ao), _stream()), "deer_head_sequence")
+    return (actions, h_n, c_n, fo, ao) if features else (actions, h_n, c_n)
+
+
+@torch.library.custom_op("deer::action_head_sequence", mutates_args=(), device_types="cuda")
+def action_head_sequence(feats: torch.Tensor, h0: Optional[torch.Tensor], c0: Optional[torch.Tensor], model: int, head: int, last_action: bool,
+                         state: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """feats (N, L, T, d) f32 -> (actions (N, L or 1, 8 A) = [pose 6 A | gripper prob A | logit A], h_n, c_n (L_lstm, N, H)): the head's
+    window mode (action_head.py:499-611) from (h0, c0) or from zero.  head 0 = extra_exit, k >= 1 = per-layer head k (layerwise_exit_eval);
+    state: robot_obs rows (N, L, S) of a use_state model.  The model's own LSTM state is not touched."""
+    m = _model(model)
+    return run_head_sequence(m.lib, m._h, m.cfg, feats, h0, c0, state, head, last_action)
+
+
+@action_head_sequence.register_fake
+def _(feats, h0, c0, model, head, last_action, state=None):
+    m = _model(model)
+    _, _, _, a_shape, s_shape = head_sequence_shapes(m.cfg, feats.shape, h0, c0, state, last_action)
+    return (feats.new_empty(a_shape, dtype=torch.float32), feats.new_empty(s_shape, dtype=torch.float32),
+            feats.new_empty(s_shape, dtype=torch.float32))
 
 
 def decode_ctl(ctl: torch.Tensor):

@@ -82,6 +82,11 @@ extern "C" {
 #define DEER_THR_MEAN 1
 #define DEER_THR_MAX 2
 #define DEER_THR_COSINE 3
+/* epilogues of deer_head_seq_gemm */
+#define DEER_SEQ_EPI_NONE 0
+#define DEER_SEQ_EPI_RELU 1
+#define DEER_SEQ_EPI_TANH 2
+#define DEER_SEQ_EPI_SIGMOID_LOGIT 3
 
 /* ---- MFMA GEMM, large M:  C = epi(A[M,K] * W[N,K]^T + bias) -----------------------------------------------
  * Replaces the nn.Linear / nn.Conv2d(patch embed) calls inside open_clip's ViT-L/14 (called at
@@ -427,6 +432,28 @@ typedef struct deer_head_fused_args {
 } deer_head_fused_args;
 long deer_head_fused_granules(int B, int d, int H, int L, int n_fc, const int* fc_dim);
 int deer_head_fused(const deer_head_fused_args* args, int w_is_f32, int n_workgroups, void* stream);
+/* ---- window mode of the head (csrc/head_seq.hip): DeterministicDecoder.forward on N sequences of L steps, action_head.py:499-611 ----
+ * Layer-major pieces that deer_head_sequence (deer_model.h) chains; w_kind: 0 bf16, 1 f32, 2 fp16 weight rows (nn.Linear layout [N][K]).
+ * deer_head_seq_pool        AdaptiveMax/AvgPool1d over the T rows of each of M (sequence, step) rows (action_head.py:519-520; no key mask
+ *                           reaches the head), + emb[M][d] (the robot-state embedding, :536) when emb != NULL.  feats [M][T][d] -> X [M][d].
+ * deer_head_seq_state_u     u [M][2d] = [relu(embed_arm_state(state[:6])) ; relu(embed_gripper_state((state[6] + 1) / 2))] (:526-532),
+ *                           state [M][8] f32; embed_state (:533) is then deer_head_seq_gemm on u.
+ * deer_head_seq_gemm        out[m][n] = epi(X[m] . W[n] + bias[n]) (nn.Linear, :86-136): MFMA, 16-bit weights against the hi + lo
+ *                           planes of the f32 activations, f32 weights on the f32 MFMA.  DEER_SEQ_EPI_SIGMOID_LOGIT also stores the
+ *                           logit at out[m][N + n].  K % 8 == 0, ldx % 8 == 0.
+ * deer_head_seq_lstm_step   one step of one nn.LSTM layer over N rows (torch gate order i, f, g, o): gates = pre[m] + h_prev[m] W_hh^T + b_hh,
+ *                           c_state [N][H] updated in place, h to h_out (row stride ld_out), (h_n, c_n) [N][H] too when not NULL;
+ *                           h_prev NULL = zero state.  H % 16 == 0.
+ * deer_head_seq_ln          LayerNorm of M rows of n values (LayerNormLSTM :44-53, MLP LayerNorm :97-103), ReLU when relu != 0; in place allowed. */
+int deer_head_seq_pool(const float* feats, const float* emb, float* X, int M, int T, int d, int avg, void* stream);
+int deer_head_seq_state_u(const float* state, const float* w_arm, const float* b_arm, const float* e_grip, float* u, int M, int d,
+                          void* stream);
+int deer_head_seq_gemm(const float* X, long ldx, const void* W, int w_kind, const float* bias, float* out, long ldo, int M, int N, int K,
+                       int epi, void* stream);
+int deer_head_seq_lstm_step(const float* pre, long ld_pre, const float* h_prev, long ld_h, const void* w_hh, int w_kind, const float* b_hh,
+                            float* c_state, float* h_out, long ld_out, float* h_n, float* c_n, int N, int H, void* stream);
+int deer_head_seq_ln(const float* src, long ld_src, float* dst, long ld_dst, const float* w, const float* b, int M, int n, float eps, int relu,
+                     void* stream);
 /* ExitController.set_timestep (eval_utils.py:662-663) + per-step reset.  step_info: device int32[4] = {hold, step sequence
  * number, host mirror pointer lo, hi} or NULL (no stage hold, no mirror). */
 int deer_ctl_begin_step(int* ctl, const int* step_info, int B, void* stream);

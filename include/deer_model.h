@@ -158,6 +158,25 @@ int deer_head_eval(deer_model* m, int layer, int T, int kind, int slot, int forc
  * hidden[layer] from ITS LSTM state (workspace "lw_state": [head][h, c][L][n_envs][H]); outputs in "action_dbg", new state in h_tmp / c_tmp */
 int deer_model_layerwise_head(const deer_model* m, int layer);
 int deer_head_eval_layerwise(deer_model* m, int head, int layer, int T, int use_mask, void* stream);
+/* Window mode of the head: DeterministicDecoder.forward on a batch of feature sequences (action_head.py:499-611, the branch :588-595) -
+ * pool every time step over its T rows (:519-520), + the robot-state embedding (use_state, :524-536), the (LayerNorm-)LSTM along the
+ * sequence from (h0, c0) or from zero, both MLP heads on every step (or on the last one: last_action, :596-597).
+ *   head    0 = extra_exit; k >= 1 = the k-th per-layer head of layerwise_exit_eval (deer_model_layerwise_head's numbering)
+ *   feats   device f32 [N][L][T][d]; h0 / c0: device f32 [L_lstm][N][H] or both NULL (zero state)
+ *   state   device f32 [N][L][8] (robot_obs[:6], robot_obs[-1], pad) - required on a use_state model (with DEER_SEQ_STATE), else NULL
+ *   flags   DEER_SEQ_LAST_ACTION | DEER_SEQ_STATE
+ *   actions device f32 [N][L or 1][8 A] = [pose 6 A | gripper prob A | logit A]; h_n / c_n: [L_lstm][N][H] or both NULL
+ * The model's LSTM state, control blocks and workspace are not touched.  Scratch: device memory the model allocates at the first call
+ * (and grows for a larger one; host only then - not capturable) and keeps until deer_model_destroy.  Calls of more than 2048 (N L) rows
+ * run in chunks of whole sequences.  DEER_ERR_SHAPE: a bad argument, a head the model lacks, state missing on a use_state model.
+ * deer_head_sequence_ex also returns the pooled (+ state) features feat_out [N][L][d] (the reference's org_feat) and the LSTM output
+ * agg_out [N][L or 1][H] (x, return_aggregate_feature) when those are not NULL. */
+#define DEER_SEQ_LAST_ACTION 1
+#define DEER_SEQ_STATE 2
+int deer_head_sequence(deer_model* m, int head, const float* feats, int N, int L, int T, const float* h0, const float* c0, const float* state,
+                       int flags, float* actions, float* h_n, float* c_n, void* stream);
+int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, int L, int T, const float* h0, const float* c0, const float* state,
+                          int flags, float* actions, float* h_n, float* c_n, float* feat_out, float* agg_out, void* stream);
 /* whole control step on ONE stream (vision batched): begin + vision + media K/V + trunk + heads */
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream);
 /* layers of the dynamic step: returns n and fills need_pseudo[i], is_exit[i], slot[i] for i < n (host only) */
