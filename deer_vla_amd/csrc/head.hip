@@ -962,7 +962,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
             const float dd = fabsf(outv[i] - prev[i]);
             if (thr_type == THR_L2) acc += dd * dd;
             else if (thr_type == THR_MEAN) acc += dd;
-            else acc = fmaxf(acc, dd);
+            else acc = (dd > acc || dd != dd) ? dd : acc;   // NaN-propagating like the protocol section below
           }
           delta = (thr_type == THR_L2) ? sqrtf(acc / NP) : (thr_type == THR_MEAN ? acc / NP : acc);
         }
@@ -1050,7 +1050,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
               const float d = fabsf(cur[i] - prev[i]);
               if (thr_type == THR_L2) acc += d * d;
               else if (thr_type == THR_MEAN) acc += d;
-              else acc = fmaxf(acc, d);
+              else acc = (d > acc || d != d) ? d : acc;     // torch's delta.max(-1) propagates a NaN (then leq never fires); fmaxf drops it
             }
             delta = (thr_type == THR_L2) ? sqrtf(acc / 6.f) : (thr_type == THR_MEAN ? acc / 6.f : acc);
           }

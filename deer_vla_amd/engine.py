@@ -16,6 +16,7 @@ runs in this repo's hand-written gfx950 kernels.
 from __future__ import annotations
 
 import ctypes
+import gc
 import os
 import time
 from contextlib import contextmanager
@@ -87,10 +88,18 @@ _GATE = _StepGate()
 @contextmanager
 def _capture(graph):
     """HIP-graph capture while no other host thread is inside an engine step (see _StepGate); thread-local error mode so that other
-    threads' allocations / copies outside a step do not invalidate it."""
+    threads' allocations / copies outside a step do not invalidate it.  The cyclic garbage collector stays off while the capture runs
+    (torch.cuda.graph collects right before it begins): a collection inside it may finalize an unreachable engine, whose device
+    synchronize and frees (DeerEngine.__del__) are illegal during a capture and abort the process."""
     with _GATE.exclusive():
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            yield
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+                yield
+        finally:
+            if gc_was_on:
+                gc.enable()
 from ._abi import config_to_c  # noqa: F401  (re-exported: tests / tools import it from here)
 from .config import DeerConfig
 from .synthetic import mlp_layer_indices
