@@ -169,8 +169,13 @@ __device__ __forceinline__ void resadd_ln_body(float* __restrict__ x, const floa
       if (beta != nullptr) y = ln_add4(y, bv[j]);
       if (out_bf != nullptr) {
         uint32_t h01, h23, l01, l23;
-        split2<F16>(y.x, y.y, h01, l01);
-        split2<F16>(y.z, y.w, h23, l23);
+        if (out_lo != nullptr) {
+          split2<F16>(y.x, y.y, h01, l01);
+          split2<F16>(y.z, y.w, h23, l23);
+        } else {                  // one 16-bit output: plain round to nearest even (fp16: +-inf past 65520, like .half() and the multi-row kernel)
+          h01 = pack2x<F16>(y.x, y.y);
+          h23 = pack2x<F16>(y.z, y.w);
+        }
         // packed: MFMA-fragment order [k-tile][lane = 16 * (k % 32 / 8) + row][8] - the <= 16 rows of one environment read back as ONE
         // contiguous 1 KiB per k-tile and plane (deer_trunk_wide_gemm, deer_xattn_fused_packed)
         const int col = i4 * 4;
