@@ -661,7 +661,13 @@ class DeerEngine:
             mtag = (mask.data_ptr(), mask._version, B * T)
             if mtag != getattr(self, "_mask_tag", None):
                 m = mask.reshape(B, T).to(torch.uint8)
-                self._mask_any_pad = bool((m == 0).any())
+                any_pad = bool((m == 0).any())
+                # a masked key 0 leaves query row 0 without a visible key: the reference fills masked scores with the finite minimum (a
+                # uniform row over all T keys), the trunk's attention kernels mask with -inf (a NaN row) - refused instead of computed
+                # differently.  Right-padded instructions (the reference's tokenizer setting) never get here.
+                if any_pad and bool((m[:, 0] == 0).any()):
+                    raise ValueError("attention mask with key 0 masked (left padding / an empty instruction) is not supported: pad on the right")
+                self._mask_any_pad = any_pad
                 self.key_mask[:B * T].copy_(m.reshape(-1), non_blocking=True)
                 self._mask_tag, self._mask_keep = mtag, mask
             use_mask = self._mask_any_pad
