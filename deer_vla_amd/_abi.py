@@ -156,6 +156,14 @@ SIGNATURES = {
     "deer_head_seq_ln": [P, L, P, L, P, P, I, I, F, I, P],
     "deer_head_sequence": [P, I, P, I, I, I, P, P, P, I, P, P, P, P],
     "deer_head_sequence_ex": [P, I, P, I, I, I, P, P, P, I, P, P, P, P, P, P],
+    # threshold calibration as one device pass (csrc/calib.hip, include/deer_model.h deer_calibrate_values)
+    "deer_calib_pool_layers": [P, L, P, I, P, I, I, I, I, P],
+    "deer_calib_gather": [P, P, P, I, P, P, I, I, I, I, P],
+    "deer_calib_lstm_step": [P, L, P, L, P, L, P, P, P, I, P, P, L, P, L, I, I, P],
+    "deer_calib_delta": [P, L, I, I, I, I, P, L, P],
+    "deer_pool_exit_layers": [P, I, I, P, P],
+    "deer_calibrate_values": [P, P, P, I, I, I, P, P, P],
+    "deer_model_scratch_bytes": [P],
     "deer_model_n_chains": [P],
     "deer_prof_enable": [P, I],
     "deer_prof_count": [P],
@@ -165,7 +173,7 @@ SIGNATURES = {
     "deer_step_plan_destroy": [P],
 }
 _RESTYPE = {"deer_head_fused_granules": c_long, "deer_hip_arch": c_char_p, "deer_model_arena_bytes": c_long, "deer_model_workspace_bytes": c_long, "deer_preprocess_scratch_bytes": c_long,
-            "deer_model_destroy": None, "deer_step_plan_destroy": None}
+            "deer_model_scratch_bytes": c_long, "deer_model_destroy": None, "deer_step_plan_destroy": None}
 
 # constants of include/deer_hip.h
 CTL_EXIT_FLAG, CTL_EXIT_LAYER, CTL_CUR_EXIT_ID, CTL_HOLD, CTL_N_EVALS, CTL_SHADOW, CTL_COMMITTED, CTL_ALL_EXITED = 0, 1, 2, 3, 4, 5, 6, 7

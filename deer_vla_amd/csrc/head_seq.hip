@@ -279,6 +279,7 @@ __global__ __launch_bounds__(256) void seq_ln_kernel(const float* src, long ld_s
 
 }  // namespace
 
+#ifndef DEER_BODIES_ONLY   // csrc/calib.hip includes the fragment helpers and kernels above, not the entry points
 extern "C" int deer_head_seq_pool(const float* feats, const float* emb, float* X, int M, int T, int d, int avg, void* stream) {
   if (feats == nullptr || X == nullptr || M <= 0 || M > 65535 || T <= 0 || d <= 0) return DEER_ERR_SHAPE;
   hipLaunchKernelGGL(seq_pool_kernel, dim3((d + 255) / 256, M), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), feats, emb, X, T, d, avg);
@@ -338,3 +339,4 @@ extern "C" int deer_head_seq_ln(const float* src, long ld_src, float* dst, long 
   DEER_LAUNCH_CHECK();
   return DEER_OK;
 }
+#endif  // DEER_BODIES_ONLY

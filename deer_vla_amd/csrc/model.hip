@@ -216,6 +216,8 @@ struct deer_model {
   size_t ghh = 0;
   void* seq_scratch = nullptr;      // deer_head_sequence: device scratch of the window-mode head, allocated at first use and grown on demand
   size_t seq_bytes = 0;
+  void* calib_scratch = nullptr;    // deer_calibrate_values: device scratch of the calibration pass, same rule
+  size_t calib_bytes = 0;
   bool head_pre = true;             // recurrent half of the LSTM head once per control step (DEER_HEAD_PRE=0: every evaluation streams W_hh again)
   bool ghh_valid = false;           // the pre-pass result matches h_state: set by deer_begin_step, cleared by deer_model_head_state_changed
   bool compact = true;              // env batches: compaction of exited environments (DEER_COMPACT=0 / deer_model_set_compaction)
@@ -1588,6 +1590,7 @@ void deer_model_destroy(deer_model* m) {
   if (m == nullptr) return;
   for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
   if (m->seq_scratch != nullptr) (void)hipFree(m->seq_scratch);
+  if (m->calib_scratch != nullptr) (void)hipFree(m->calib_scratch);
   delete m;
 }
 
@@ -1957,6 +1960,142 @@ int deer_head_sequence(deer_model* m, int head, const float* feats, int N, int L
                        int flags, float* actions, float* h_n, float* c_n, void* stream) {
   return deer_head_sequence_ex(m, head, feats, N, L, T, h0, c0, state, flags, actions, h_n, c_n, nullptr, nullptr, stream);
 }
+
+// ---- threshold calibration as one device pass (csrc/calib.hip) ------------------------------------------------------------------------
+// candidate layers [0] + exits (value_net.py:139: `for i in [0] + self.exit_list`); -1: no exits / layer 0 among them (value_net.py:135)
+static int calib_layers(const deer_model* m, int* lay) {
+  const int ne = (int)m->exit_ids.size();
+  if (ne < 1 || ne + 1 > DEER_CALIB_MAX_NL || m->c.n_layers > DEER_CALIB_MAX_LAYERS) return -1;
+  lay[0] = 0;
+  for (int k = 0; k < ne; ++k) {
+    if (m->exit_ids[k] <= 0 || m->exit_ids[k] >= m->c.n_layers) return -1;
+    lay[k + 1] = m->exit_ids[k];
+  }
+  return ne + 1;
+}
+
+// The reads generate_action_values makes of the window-mode hidden states (value_net.py:375-386 hands all of them to the value net;
+// action_head.py:519-520 pools each (frame, layer) it is given): P[frame][k] = pooled hidden_states[[0] + exits][frame].
+int deer_pool_exit_layers(deer_model* m, int n_frames, int T, float* P, void* stream) {
+  const deer_config& c = m->c;
+  if (m->ws == nullptr || P == nullptr || n_frames <= 0 || n_frames > m->B || T <= 0 || T > c.max_text_len) return DEER_ERR_SHAPE;
+  const long rows_cap = std::min(m->B * c.max_text_len, kMaxRows);
+  if ((long)n_frames * T > rows_cap) return DEER_ERR_SHAPE;
+  int lay[DEER_CALIB_MAX_NL];
+  const int NL = calib_layers(m, lay);
+  if (NL < 0) return DEER_ERR_SHAPE;
+  Bracket b(m, "deer_pool_exit_layers", 0, (double)NL * n_frames * (T + 1) * m->d * 4, stream);
+  return deer_calib_pool_layers(m->Wk<float>(m->hidden), rows_cap * m->d, lay, NL, P, n_frames, T, m->d, c.pooling_avg, stream);
+}
+
+// ActionValueNet.forward(mode='generate') (value_net.py:134-160) with get_delta (:105-117) on DeterministicDecoder (action_head.py:499-611):
+// history + candidates, layer-major (see csrc/calib.hip).  Rows of a chunk of bc windows: Rh = bc (W - 1) history rows (b, t), then
+// Rc = NL bc S candidate rows (k, b, s), S = W - W/2.
+int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers, int bs, int W, int threshold_type, float* values,
+                          float* actions, void* stream) {
+  const deer_config& c = m->c;
+  if (m->arena == nullptr || P == nullptr || rand_layers == nullptr || values == nullptr || bs <= 0 || W < 2 || threshold_type < 0 ||
+      threshold_type > 3 || c.use_state)
+    return DEER_ERR_SHAPE;
+  int lay[DEER_CALIB_MAX_NL], slot_of[DEER_CALIB_MAX_LAYERS];
+  const int NL = calib_layers(m, lay);
+  if (NL < 0) return DEER_ERR_SHAPE;
+  for (int l = 0; l < c.n_layers; ++l) slot_of[l] = -1;
+  for (int k = 0; k < NL; ++k) slot_of[lay[k]] = k;
+  const int d = m->d, H = m->H, Lh = m->Lh, A = std::max(1, c.multi_step_action), wk = m->wkind;
+  const int S = W - W / 2, L = W - 1;
+  const int fc_max = m->n_fc > 0 ? m->fc_dims[0] : H;
+  if ((long)bs * S > 0x7fffffffL / (8 * A * NL)) return DEER_ERR_SHAPE;
+  const int bc = (int)std::max(1L, std::min((long)bs, kSeqRows / L));
+  const long Rh = (long)bc * L, Rc = (long)NL * bc * S, R = Rh + Rc;
+  if (R > 0x7fffffffL / (4 * std::max(H, d))) return DEER_ERR_SHAPE;
+  // scratch (floats): X [R][max(d, H)], pre [R][4H], y [R][H], c [Rh][H], zero row [H], two MLP buffers per head [Rc][fc_max],
+  // actions [Rc][8A]; then the candidate -> history row index, int [Rc]
+  const long xw = std::max(d, H);
+  const long n_x = R * xw, n_pre = R * 4 * H, n_y = R * H, n_c = Rh * H, n_z = Rc * fc_max, n_act = Rc * 8 * A;
+  const size_t need = (size_t)(n_x + n_pre + n_y + n_c + H + 4 * n_z + n_act + Rc) * sizeof(float) + 16 * 256;
+  hipStream_t st = (hipStream_t)stream;
+  if (need > m->calib_bytes) {                          // host only: the first call (or a larger one) allocates
+    if (m->calib_scratch != nullptr) {
+      if (hipStreamSynchronize(st) != hipSuccess) return DEER_ERR_LAUNCH;
+      (void)hipFree(m->calib_scratch);
+      m->calib_scratch = nullptr;
+      m->calib_bytes = 0;
+    }
+    if (hipMalloc(&m->calib_scratch, need) != hipSuccess) return DEER_ERR_LAUNCH;
+    m->calib_bytes = need;
+  }
+  char* base = reinterpret_cast<char*>(m->calib_scratch);
+  size_t off = 0;
+  auto take = [&](long n) { float* p = reinterpret_cast<float*>(base + off); off += ((size_t)n * sizeof(float) + 255) & ~size_t(255); return p; };
+  float* X = take(n_x);
+  float* PRE = take(n_pre);
+  float* Y = take(n_y);
+  float* CS = take(n_c);
+  float* HZ = take(H);
+  float* Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
+  float* ACT = take(n_act);
+  int* IDX = reinterpret_cast<int*>(take(Rc));
+  if (hipMemsetAsync(HZ, 0, (size_t)H * sizeof(float), st) != hipSuccess) return DEER_ERR_LAUNCH;
+  const long n_val = (long)bs * S;                      // row length of `values` and rows per candidate layer of `actions`
+  for (int b0 = 0; b0 < bs; b0 += bc) {
+    const int nb = std::min(bc, bs - b0);
+    const long rh = (long)nb * L, rc = (long)NL * nb * S, rows = rh + rc;
+    DEER_TRY(deer_calib_gather(P + (long)b0 * W * NL * d, rand_layers + (long)b0 * W, slot_of, c.n_layers, X, IDX, nb, W, NL, d, stream));
+    for (int l = 0; l < Lh; ++l) {
+      const LstmW& Lw = m->lstm[l];
+      const float* xin = X;
+      int in_dim = d;
+      if (l > 0) {
+        in_dim = H;
+        if (c.lstm_layernorm) DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(m->lstm[l - 1].lnw), m->A<float>(m->lstm[l - 1].lnb), (int)rows, H, kEps, 0, stream));
+        else xin = Y;
+      }
+      // W_ih of this layer once for history and candidate rows
+      DEER_TRY(deer_head_seq_gemm(xin, in_dim, m->A<void>(Lw.wih), wk, m->A<float>(Lw.bih), PRE, 4L * H, (int)rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+      // history: step t of every window from its step t - 1, (h, c) of every step kept in Y / CS rows (b, t)
+      for (int t = 0; t < L; ++t)
+        DEER_TRY(deer_calib_lstm_step(PRE + (long)t * 4 * H, (long)L * 4 * H, t > 0 ? Y + (long)(t - 1) * H : nullptr, (long)L * H,
+                                      t > 0 ? CS + (long)(t - 1) * H : nullptr, (long)L * H, nullptr, nullptr, m->A<void>(Lw.whh), wk,
+                                      m->A<float>(Lw.bhh), CS + (long)t * H, (long)L * H, Y + (long)t * H, (long)L * H, nb, H, stream));
+      // candidates: one step of every (layer, window, seq_id) row from the history state after step seq_id - 1
+      DEER_TRY(deer_calib_lstm_step(PRE + rh * 4 * H, 4L * H, Y, H, CS, H, IDX, HZ, m->A<void>(Lw.whh), wk, m->A<float>(Lw.bhh), nullptr, 0,
+                                    Y + rh * H, H, (int)rc, H, stream));
+    }
+    // ---- the candidates' LSTM output (LayerNorm'ed with lstm_layernorm) -> the two MLP heads (action_head.py:86-136) ----
+    const float* xo = Y + rh * H;
+    if (c.lstm_layernorm) {
+      DEER_TRY(deer_head_seq_ln(Y + rh * H, H, X, H, m->A<float>(m->lstm.back().lnw), m->A<float>(m->lstm.back().lnb), (int)rc, H, kEps, 0, stream));
+      xo = X;
+    }
+    const int mr = (int)rc;
+    for (int g = 0; g < 2; ++g) {
+      const float* src = xo;
+      long lds = H;
+      int kin = H;
+      for (int fi = 0; fi < m->n_fc; ++fi) {
+        const FcW& F = m->fc[fi];
+        const int dim = m->fc_dims[fi];
+        float* z = Z[g][fi & 1];
+        DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(F.w[g]), wk, m->A<float>(F.b[g]), z, dim, mr, dim, kin,
+                                    c.mlp_layernorm ? DEER_SEQ_EPI_NONE : DEER_SEQ_EPI_RELU, stream));
+        if (c.mlp_layernorm) DEER_TRY(deer_head_seq_ln(z, dim, z, dim, m->A<float>(F.lnw[g]), m->A<float>(F.lnb[g]), mr, dim, kEps, 1, stream));
+        src = z; lds = dim; kin = dim;
+      }
+      if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(m->wa), wk, m->A<float>(m->ba), ACT, 8L * A, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
+      else DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(m->wg), wk, m->A<float>(m->bg), ACT + 6 * A, 8L * A, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
+    }
+    // ---- deltas of consecutive candidate layers over the 6 A pose values, window-major columns b0 S .. ----
+    DEER_TRY(deer_calib_delta(ACT, 8L * A, NL, nb * S, 6 * A, threshold_type, values + (long)b0 * S, n_val, stream));
+    if (actions != nullptr &&
+        hipMemcpy2DAsync(actions + (long)b0 * S * 8 * A, (size_t)n_val * 8 * A * sizeof(float), ACT, (size_t)nb * S * 8 * A * sizeof(float),
+                         (size_t)nb * S * 8 * A * sizeof(float), NL, hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return DEER_ERR_LAUNCH;
+  }
+  return DEER_OK;
+}
+
+long deer_model_scratch_bytes(const deer_model* m) { return (long)(m->seq_bytes + m->calib_bytes); }
 
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream) {
   if (m->ws == nullptr || T <= 0 || T > m->c.max_text_len || m->B * T > kMaxRows || exit_id >= m->c.n_layers) return DEER_ERR_SHAPE;

@@ -1117,6 +1117,59 @@ class DeerEngine:
             cur.wait_stream(self._side_stream)
         return out
 
+    def window_exit_features(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8) -> torch.Tensor:
+        """``window_hidden_states`` reduced to what the calibration reads: the POOLED feature (max / mean over the T rows,
+        action_head.py:519-520; all T rows - no mask reaches the head) of layer 0 and of every exit layer, (F, NL, d) fp32 on the device with
+        NL = 1 + n_exit - ``n_layers * T / NL`` times less than the (F, n_layers, T, d) hidden states.  The same grouped static full-depth pass
+        (two alternating siblings on two streams); each group ends in one ``deer_pool_exit_layers`` launch instead of the permuted copy."""
+        F = rgb_seq.shape[0]
+        ids = ids.reshape(-1, ids.shape[-1])
+        T = ids.shape[1]
+        G = max(1, min(group, self.MAX_ROWS // T, F, abi.MAX_ENVS))
+        last = self.cfg.n_layers - 1
+        NL, d = len(self.exit_ids) + 1, self.cfg.d_model
+        n_groups = (F + G - 1) // G
+        out = torch.empty(n_groups * G, NL, d, device=self.dev)    # whole groups: the padded frames of the last one are cut off below
+        ws = [self.sibling(G)] + ([self.sibling(G, 1)] if n_groups > 1 else [])
+        cur = torch.cuda.current_stream()
+        sts = [cur] + ([self._side_stream] if n_groups > 1 else [])
+        for w in ws:
+            w._drain_side_streams()
+            if list(w.exit_ids) != list(self.exit_ids):           # the pooled layers are the sibling model's configured exits
+                w.configure_exit(self.exit_ids, self.exit_ids[-1] + 1)
+        if n_groups > 1:
+            self._side_stream.wait_stream(cur)                    # inputs produced on the caller's stream
+        for gi, f0 in enumerate(range(0, F, G)):
+            w, st = ws[gi % len(ws)], sts[gi % len(ws)]
+            with torch.cuda.stream(st):
+                idx = [min(f0 + i, F - 1) for i in range(G)]      # the last group is padded with its last frame
+                ids_g = ids[idx] if ids.shape[0] == F else ids.expand(G, T)
+                mask_g = None
+                if mask is not None:
+                    m2 = mask.reshape(-1, T)
+                    mask_g = m2[idx] if m2.shape[0] == F else m2.expand(G, T)
+                T_, use_mask = w.load_inputs(rgb_seq[idx], grip_seq[idx], ids_g.contiguous(), mask_g)
+                w.hold_dev.zero_()
+                w._enqueue_step(T_, use_mask, last)               # static full depth: every layer's output is kept
+                abi.check(w.lib.deer_pool_exit_layers(w._h, G, T_, abi.ptr(out[f0:f0 + G]), _cur_stream()), "deer_pool_exit_layers")
+        if n_groups > 1:
+            cur.wait_stream(self._side_stream)
+        return out[:F]
+
+    def calibrate_values(self, feats: torch.Tensor, rand_layers, threshold_type: str = "L2", return_actions: bool = False):
+        """``ActionValueNet.forward(mode='generate')`` (value_net.py:134-160) as ONE spine call (include/deer_model.h deer_calibrate_values,
+        csrc/calib.hip) on pooled features: feats (bs, W, NL, d) from ``window_exit_features`` (or (W, NL, d) for one window), rand_layers
+        (bs, W) / (W,) the random exit layer of every step -> values (n_exit, bs * (W - W/2)) ON THE DEVICE, window-major like
+        ``generate_values``; return_actions=True also returns the candidates' actions (NL, bs, W - W/2, 8 A).  Any bs (chunked inside the
+        spine).  Against the per-step loop of ``generate_values`` it pays from bs = 2 windows on; the engine's committed LSTM
+        state does not change.  A use_state model raises NotImplementedError."""
+        from .ops import run_calibrate_values
+        f = feats.to(device=self.dev)
+        if f.dim() == 3:
+            f = f.unsqueeze(0)
+        rl = torch.as_tensor(rand_layers).reshape(f.shape[0], -1)
+        return run_calibrate_values(self.lib, self._h, self.cfg, self.exit_ids, f, rl, threshold_type, return_actions)
+
     def _head_eval(self, feats: torch.Tensor, commit: bool) -> torch.Tensor:
         """One DeterministicDecoder step of all n_envs sequences on ``feats`` (n_envs*T, d) from the current LSTM state; commit=True
         stores the new state (update_hidden_state protocol, action_head.py:548-558).  Returns the device rows [pose6, gripper prob,

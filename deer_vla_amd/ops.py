@@ -10,6 +10,9 @@ through PyTorch-ROCm custom ops").  These are the three coarse operators SURVEY.
   deer::action_head_sequence(Tensor feats, Tensor? h0, Tensor? c0, int model, int head, bool last_action, Tensor? state=None)
                                         -> (Tensor actions, Tensor h_n, Tensor c_n) DeterministicDecoder.forward on sequences
                                                                                (action_head.py:499-611, window mode :588-595)
+  deer::calibrate_values(Tensor feats, Tensor rand_layers, int model, str threshold_type) -> Tensor values
+                                                                               ActionValueNet.forward(mode='generate')
+                                                                               (value_net.py:134-160) on pooled exit-layer features
 
 ``model`` is the address of a ``deer_model`` (``NativeModel.handle``): weights, workspace, LSTM state and the exit controller
 configuration live in that object, like they live in the reference's stateful ``MPTFlamingo`` module.
@@ -68,6 +71,7 @@ class NativeModel:
         if n:
             raise abi.DeerHipError(f"{n} required parameters missing, e.g. {buf.value.decode().split()[:4]}")
         self.buffer("thresholds").view(torch.float32).fill_(1e8)
+        self.exit_ids = list(cfg.exit_ids())                # the model's default exits until configure_exit
         _MODELS[self.handle] = self
 
     @property
@@ -84,6 +88,7 @@ class NativeModel:
         ids = (ctypes.c_int * len(exit_ids))(*exit_ids)
         abi.check(self.lib.deer_model_configure_exit(self._h, ids, len(exit_ids), max_layer, abi.THR_TYPES[threshold_type], 1 if leq else 0),
                   "deer_model_configure_exit")
+        self.exit_ids = list(exit_ids)
         if thresholds is not None:
             t = torch.full((16,), 1e8, dtype=torch.float32)
             t[: len(thresholds)] = torch.tensor([float(v) for v in thresholds])
@@ -238,6 +243,75 @@ def _(feats, h0, c0, model, head, last_action, state=None):
     _, _, _, a_shape, s_shape = head_sequence_shapes(m.cfg, feats.shape, h0, c0, state, last_action)
     return (feats.new_empty(a_shape, dtype=torch.float32), feats.new_empty(s_shape, dtype=torch.float32),
             feats.new_empty(s_shape, dtype=torch.float32))
+
+
+def calib_layer_slots(exit_ids: Sequence[int], n_layers: int):
+    """Layer -> slot table of the calibration pass: the candidate layers are [0] + exit_ids (value_net.py:139), slot k of the pooled
+    features (.., NL, d) holds candidate layer k; every other layer has no slot (-1).  Layer 0 must not be an exit (value_net.py:135)."""
+    ids = [int(e) for e in exit_ids]
+    if not ids or any(e <= 0 or e >= n_layers for e in ids) or any(b <= a for a, b in zip(ids, ids[1:])):
+        raise ValueError(f"calibration: the exits must be increasing layers in [1, {n_layers}) (layer 0 is the first candidate, not an exit), got {ids}")
+    slots = [-1] * n_layers
+    for k, layer in enumerate([0] + ids):
+        slots[layer] = k
+    return slots
+
+
+def calibrate_shapes(cfg, exit_ids: Sequence[int], feats_shape, rand_layers, threshold_type: str = "L2"):
+    """Host-side checks of a calibration call (no device touched): feats (bs, W, NL, d) pooled features of the candidate layers [0] + exit_ids,
+    rand_layers (bs, W) the random EXIT layer of every step (checked here when it lives on the host; on the device a layer without a slot
+    makes its window's values NaN).  Returns (bs, W, NL, S = W - W/2, A)."""
+    if getattr(cfg, "use_state", False):
+        raise NotImplementedError("calibration of a use_state head: the reference's dynamic exit cannot run with use_state (value_net.py:122-129 "
+                                  "calls the head without the robot state), so its thresholds have no consumer")
+    if threshold_type not in abi.THR_TYPES:
+        raise NotImplementedError(threshold_type)
+    slots = calib_layer_slots(exit_ids, cfg.n_layers)
+    NL = len(exit_ids) + 1
+    if len(feats_shape) != 4:
+        raise ValueError(f"calibrate_values: feats must be (bs, W, NL, d), got {tuple(feats_shape)}")
+    bs, W, nl, d = (int(v) for v in feats_shape)
+    if bs < 1 or W < 2:
+        raise ValueError(f"calibrate_values: needs bs >= 1 windows of W >= 2 steps, got bs = {bs}, W = {W}")
+    if nl != NL or d != cfg.d_model:
+        raise ValueError(f"calibrate_values: feats (bs, W, NL, d) = {tuple(feats_shape)} for the {NL} candidate layers {[0] + list(exit_ids)} "
+                         f"and d_model {cfg.d_model}")
+    if tuple(rand_layers.shape) != (bs, W):
+        raise ValueError(f"calibrate_values: rand_layers must be (bs, W) = {(bs, W)}, got {tuple(rand_layers.shape)}")
+    if rand_layers.device.type == "cpu":
+        bad = [int(v) for v in rand_layers.reshape(-1).tolist() if not (0 <= int(v) < cfg.n_layers and slots[int(v)] > 0)]
+        if bad:
+            raise ValueError(f"calibrate_values: rand_layers holds {sorted(set(bad))}, not exit layers {list(exit_ids)}")
+    return bs, W, NL, W - W // 2, max(1, int(getattr(cfg, "multi_step_action", 1)))
+
+
+def run_calibrate_values(lib, handle, cfg, exit_ids, feats: torch.Tensor, rand_layers, threshold_type: str = "L2", return_actions: bool = False):
+    """One ``deer_calibrate_values`` call on the current stream: values (n_exit, bs * (W - W/2)) on the device[, actions (NL, bs, W - W/2, 8 A)]."""
+    rl = torch.as_tensor(rand_layers)
+    bs, W, NL, S, A = calibrate_shapes(cfg, exit_ids, feats.shape, rl, threshold_type)
+    dev = feats.device
+    f = feats.to(torch.float32).contiguous()
+    rl_d = rl.to(device=dev, dtype=torch.int32).contiguous()
+    values = torch.empty(NL - 1, bs * S, dtype=torch.float32, device=dev)
+    actions = torch.empty(NL, bs, S, 8 * A, dtype=torch.float32, device=dev) if return_actions else None
+    abi.check(lib.deer_calibrate_values(handle, abi.ptr(f), abi.ptr(rl_d), bs, W, abi.THR_TYPES[threshold_type], abi.ptr(values), abi.ptr(actions),
+                                        _stream()), "deer_calibrate_values")
+    return (values, actions) if return_actions else values
+
+
+@torch.library.custom_op("deer::calibrate_values", mutates_args=(), device_types="cuda")
+def calibrate_values(feats: torch.Tensor, rand_layers: torch.Tensor, model: int, threshold_type: str) -> torch.Tensor:
+    """feats (bs, W, NL, d) pooled features of the candidate layers [0] + exits (deer_pool_exit_layers), rand_layers (bs, W) int -> the
+    deltas between consecutive exits (n_exit, bs * (W - W/2)), window-major (value_net.py:134-160).  The model's LSTM state is not touched."""
+    m = _model(model)
+    return run_calibrate_values(m.lib, m._h, m.cfg, m.exit_ids, feats, rand_layers, threshold_type)
+
+
+@calibrate_values.register_fake
+def _(feats, rand_layers, model, threshold_type):
+    m = _model(model)
+    bs, W, NL, S, _ = calibrate_shapes(m.cfg, m.exit_ids, feats.shape, rand_layers, threshold_type)
+    return feats.new_empty((NL - 1, bs * S), dtype=torch.float32)
 
 
 def decode_ctl(ctl: torch.Tensor):

@@ -153,11 +153,12 @@ class ExitController:
         self._version += 1
         return values
 
-    def set_threshold(self, args, model, dataloader, exit_ratio, model_name, values=None):
-        """value_net.py:185-264: deltas over the calibration loader (every rank its share, all-gathered), then the solver."""
+    def set_threshold(self, args, model, dataloader, exit_ratio, model_name, values=None, fused=False):
+        """value_net.py:185-264: deltas over the calibration loader (every rank its share, all-gathered), then the solver.
+        fused=True: the calibration as one device pass per batch (``generate_action_values(fused=True)``)."""
         if values is None:
             from .distributed import all_gather_values
-            pred, _ = generate_action_values(args, model, self.value_net, dataloader, device_id=None)
+            pred, _ = generate_action_values(args, model, self.value_net, dataloader, device_id=None, fused=fused)
             values = all_gather_values(pred)
         return self.set_threshold_from_values(values, exit_ratio, model_name)
 
@@ -218,13 +219,16 @@ def controllers_from_values(value_net: Optional[ActionValueNet], exit_id_list: S
     return out
 
 
-def generate_action_values(args, model, value_net: ActionValueNet, calvin_loader, device_id=None, generator=None):
+def generate_action_values(args, model, value_net: ActionValueNet, calvin_loader, device_id=None, generator=None, fused=False):
     """value_net.py:301-397 on the native engine.  ``calvin_loader`` yields the reference's CALVIN batches:
     ``batch[0]`` images (bs, W, 3, S, S), ``batch[1]`` = (input_ids (bs, T), attention_mask (bs, T)), ``batch[3]`` gripper
     frames (bs, W, 3, S, S); W must equal ``value_net.window_size``.  For every window the trunk is run at full depth on each
     frame pair, the history fed to the head comes from a random exit layer per time step (flamingo_mpt.py:486-490,
     ``generator`` seeds the choice) and ``DeerEngine.generate_values`` evaluates the window-mode deltas.
-    Returns (values (n_exit, n_windows * (W - W/2)), None) like the reference."""
+    Returns (values (n_exit, n_windows * (W - W/2)), None) like the reference.
+    fused=True: the same random layers (same generator calls), but every batch keeps only the pooled features of layer 0 and the exit
+    layers (``DeerEngine.window_exit_features``) and the head side runs as one device pass (``DeerEngine.calibrate_values``, csrc/calib.hip);
+    the values then stay on the device."""
     eng = model.module.engine
     exit_ids = list(value_net.exit_list)
     W = value_net.window_size
@@ -242,6 +246,11 @@ def generate_action_values(args, model, value_net: ActionValueNet, calvin_loader
         mask = None
         if attention_mask is not None:
             mask = attention_mask.to(eng.dev).unsqueeze(1).expand(bs, W, attention_mask.shape[-1]).reshape(bs * W, -1)
+        if fused:
+            feats = eng.window_exit_features(images.reshape(bs * W, 3, S, S).to(eng.dev, eng.img_dtype),
+                                             gripper.reshape(bs * W, 3, S, S).to(eng.dev, eng.img_dtype), ids, mask)
+            out.append(eng.calibrate_values(feats.view(bs, W, *feats.shape[1:]), rand_layers, value_net.threshold_type))
+            continue
         hid = eng.window_hidden_states(images.reshape(bs * W, 3, S, S).to(eng.dev, eng.img_dtype),
                                        gripper.reshape(bs * W, 3, S, S).to(eng.dev, eng.img_dtype), ids, mask)
         hid = hid.view(bs, W, *hid.shape[1:])

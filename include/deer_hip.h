@@ -454,6 +454,29 @@ int deer_head_seq_lstm_step(const float* pre, long ld_pre, const float* h_prev, 
                             float* c_state, float* h_out, long ld_out, float* h_n, float* c_n, int N, int H, void* stream);
 int deer_head_seq_ln(const float* src, long ld_src, float* dst, long ld_dst, const float* w, const float* b, int M, int n, float eps, int relu,
                      void* stream);
+/* ---- threshold calibration as one device pass (csrc/calib.hip): ActionValueNet.forward(mode='generate'), value_net.py:134-160 ----
+ * Pieces that deer_pool_exit_layers / deer_calibrate_values (deer_model.h) chain with the window-mode GEMM / LayerNorm above.
+ * deer_calib_pool_layers    P[frame][k][d] = max / mean over the T rows of frame `frame` of hidden[layers[k]] (action_head.py:519-520, all T
+ *                           rows); hidden + layer * layer_stride + (frame * T + t) * d.  layers: HOST int[NL], NL <= DEER_CALIB_MAX_NL.  d % 4 == 0.
+ * deer_calib_gather         rows of a chunk of bc windows from P [bc][W][NL][d]: X[(b, t)] = P[b][t][slot_of_layer[rand_layers[b][t]]] for
+ *                           t < W - 1 (the history, flamingo_mpt.py:486-490), then X[bc (W - 1) + (k, b, s)] = P[b][W/2 - 1 + s][k] for
+ *                           s < W - W/2 (the candidates, value_net.py:139-153), and idx[(k, b, s)] = history row (b, W/2 - 2 + s) or -1.
+ *                           rand_layers: DEVICE int32 [bc][W]; slot_of_layer: HOST int[n_layers] (-1: no slot -> NaN row).
+ * deer_calib_lstm_step      deer_head_seq_lstm_step with a read-only previous state: row m continues from row idx[m] (idx NULL: m) of
+ *                           h_prev / c_prev (row strides ld_h / ld_c); a negative index or h_prev NULL = the zero state (zero_row: H zeros).
+ *                           c to c_out (or dropped when NULL), h to h_out.
+ * deer_calib_delta          values[e][r] = get_delta(actions[e][r], actions[e + 1][r]) (value_net.py:105-117) over the first NP values of
+ *                           each action row; actions [NL][rows][ld_act], values [NL - 1][ld_val]; thr_type 0 L2, 1 mean, 2 max, 3 cosine. */
+#define DEER_CALIB_MAX_NL 17
+#define DEER_CALIB_MAX_LAYERS 64
+int deer_calib_pool_layers(const float* hidden, long layer_stride, const int* layers, int NL, float* P, int n_frames, int T, int d, int avg,
+                           void* stream);
+int deer_calib_gather(const float* P, const int* rand_layers, const int* slot_of_layer, int n_layers, float* X, int* idx, int bc, int W,
+                      int NL, int d, void* stream);
+int deer_calib_lstm_step(const float* pre, long ld_pre, const float* h_prev, long ld_h, const float* c_prev, long ld_c, const int* idx,
+                         const float* zero_row, const void* w_hh, int w_kind, const float* b_hh, float* c_out, long ld_co, float* h_out,
+                         long ld_out, int N, int H, void* stream);
+int deer_calib_delta(const float* actions, long ld_act, int NL, int rows, int NP, int thr_type, float* values, long ld_val, void* stream);
 /* ExitController.set_timestep (eval_utils.py:662-663) + per-step reset.  step_info: device int32[4] = {hold, step sequence
  * number, host mirror pointer lo, hi} or NULL (no stage hold, no mirror). */
 int deer_ctl_begin_step(int* ctl, const int* step_info, int B, void* stream);

@@ -177,6 +177,26 @@ int deer_head_sequence(deer_model* m, int head, const float* feats, int N, int L
                        int flags, float* actions, float* h_n, float* c_n, void* stream);
 int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, int L, int T, const float* h0, const float* c0, const float* state,
                           int flags, float* actions, float* h_n, float* c_n, float* feat_out, float* agg_out, void* stream);
+/* Threshold calibration as one device pass (csrc/calib.hip): the head side of generate_action_values (value_net.py:301-397).
+ * NL = 1 + n_exit candidate layers = [0] + the configured exits (deer_model_configure_exit; value_net.py:135 asserts layer 0 is no exit).
+ * deer_pool_exit_layers   after a static full-depth step of n_frames frames (batch rows) of T tokens: P [n_frames][NL][d] = the pooled
+ *                         feature (action_head.py:519-520, max / mean over all T rows) of hidden_states[k] for k over [0] + exits - all
+ *                         the calibration reads of the (n_layers, n_frames T, d) hidden states (value_net.py:375-386).  One launch.
+ * deer_calibrate_values   ActionValueNet.forward(mode='generate') (value_net.py:134-160) on bs windows of W steps:
+ *   P            device f32 [bs][W][NL][d] pooled features;  rand_layers: device int32 [bs][W], the random exit LAYER of every step
+ *                (flamingo_mpt.py:486-490; the last step's is not read)
+ *   values       device f32 [n_exit][bs (W - W/2)], window-major like value_net.py:160; threshold_type 0 L2, 1 mean, 2 max, 3 cosine
+ *   actions      NULL, or device f32 [NL][bs][W - W/2][8 A]: the candidates' [pose 6 A | gripper prob A | logit A]
+ * Schedule: per LSTM layer one W_ih projection of history + candidate rows, W - 1 history steps, ONE step of all candidates from their
+ * window's history state; then the MLP heads on the candidates and the deltas.  More than 2048 history rows (bs (W - 1)) run in chunks
+ * of whole windows; a row's result does not depend on the chunking.  The model's LSTM state, control blocks and workspace are not touched;
+ * scratch as deer_head_sequence (allocated / grown at the call that needs it - not capturable -, freed by deer_model_destroy;
+ * deer_model_scratch_bytes: what the window-mode head and the calibration hold).  DEER_ERR_SHAPE: bad argument, W < 2, layer 0 among
+ * the exits, a use_state model (the reference's dynamic exit cannot run with use_state, value_net.py:122-129). */
+int deer_pool_exit_layers(deer_model* m, int n_frames, int T, float* P, void* stream);
+int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers, int bs, int W, int threshold_type, float* values,
+                          float* actions, void* stream);
+long deer_model_scratch_bytes(const deer_model* m);
 /* whole control step on ONE stream (vision batched): begin + vision + media K/V + trunk + heads */
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream);
 /* layers of the dynamic step: returns n and fills need_pseudo[i], is_exit[i], slot[i] for i < n (host only) */

@@ -5,7 +5,7 @@ synthetic environments and prints one JSON line per point (ratio, cap, threshold
 alone and prints the wall time of the sweep against the sum of the single-point runs.
 
 usage: sweep_operating_points.py --exit_ratio 0.6 0.8 1.0 1.2 [--max_layer 12 6] [--num_seq 16] [--n_envs 8] [--config tiny|3b]
-                                 [--ep_len 8] [--compare]"""
+                                 [--ep_len 8] [--compare] [--fused-calibration]"""
 import argparse
 import json
 import os
@@ -49,6 +49,8 @@ def main():
     ap.add_argument("--task_steps", type=int, default=4, help="steps after which a sub-task counts as solved")
     ap.add_argument("--calib_windows", type=int, default=2)
     ap.add_argument("--compare", action="store_true", help="also run every point alone and report both wall times")
+    ap.add_argument("--fused-calibration", action="store_true",
+                    help="calibrate through window_exit_features + calibrate_values (one device pass per batch) instead of the per-step loop")
     args = ap.parse_args()
 
     cfg = deer_tiny() if args.config == "tiny" else deer_3b()
@@ -59,7 +61,7 @@ def main():
     vn = ActionValueNet(exit_ids, None, cfg.exit_interval, cfg.window_size, "L2")
     t0 = time.perf_counter()
     values, _ = generate_action_values(None, model, vn, calibration_loader(cfg, proc, tok, args.calib_windows, cfg.window_size),
-                                       generator=torch.Generator().manual_seed(0))
+                                       generator=torch.Generator().manual_seed(0), fused=args.fused_calibration)
     t_cal = time.perf_counter() - t0
     caps = args.max_layer or [exit_ids[-1] + 1]
     pairs = [(r, m) for m in caps for r in args.exit_ratio]
