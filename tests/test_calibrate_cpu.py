@@ -163,3 +163,23 @@ def test_set_threshold_routes_fused(monkeypatch):
     monkeypatch.setattr("deer_vla_amd.distributed.all_gather_values", lambda v: v)
     ctl.set_threshold(None, _M(e), _loader(4, [2]), 0.8, "mpt_dolly_3b", fused=True)
     assert e.calls == ["pooled", "fused"] and len(ctl.threshold_list()) == 3
+
+
+@pytest.mark.parametrize("variant", ["ln_max", "plain", "avg", "ms2"])
+def test_cosine_condition_of_the_committed_oracle_inputs(variant):
+    """tests/test_calibrate_values.py compares cosine values with the oracle wherever both oracle actions of a pair have a norm >= 0.1, on
+    condition that at most 10 % of the pairs of a parametrisation are left out.  The oracle alone decides that, so it is checked here, on the
+    very inputs of that test (the engine's precision plays no part)."""
+    import test_calibrate_values as tcv
+    assert list(tcv.VARIANTS) == ["ln_max", "plain", "avg", "ms2"]
+    pool = tcv._tiny_oracle_hidden()
+    cfg = deer_tiny(**tcv.VARIANTS[variant])
+    head = tcv._ZeroStartHead(tcv.syn.make_synthetic_state(cfg, 3, bf16_round=True), cfg, "extra_exit.")
+    exit_ids = cfg.exit_ids()
+    pairs = left_out = 0
+    for bs in tcv.BS_TINY:
+        for W in tcv.W_TINY:
+            ok = tcv._cosine_comparable(tcv._oracle_actions(head, exit_ids, *tcv._tiny_case(pool, exit_ids, bs, W)))
+            pairs, left_out = pairs + ok.numel(), left_out + int((~ok).sum())
+    print(f"{variant}: {left_out} of {pairs} cosine pairs have an oracle action of norm < {tcv.COS_MIN_NORM}")
+    assert pairs > 0 and left_out <= tcv.COS_MAX_LEFT_OUT * pairs

@@ -45,22 +45,30 @@ class _ZeroStartHead(orc.OracleHead):
     """OracleHead with every evaluation started from the zero LSTM state - what generate mode is for every W > 2, where each call is a
     window-mode sequence.  At W = 2 the sequences have ONE step, and a one-step call takes the head's step mode, which continues from whatever
     state the previous call left behind (the previous candidate layer, or an earlier window batch): that carry-over is call history, not
-    part of generate mode, and ``DeerEngine.generate_values`` starts W = 2 from zero as well.  For W > 2 this class changes nothing."""
+    part of generate mode, and ``DeerEngine.generate_values`` starts W = 2 from zero as well.  W = 3 has one such call too: its first seq_id
+    is W/2 - 1 = 0, an empty history + the candidate's own step, so that call is a one-step sequence as at W = 2 (its seq_id = 1 calls have
+    two steps and are window mode).  For W > 3 this class changes nothing."""
 
     def __call__(self, *a, **k):
         self.clear_hidden_state()
         return super().__call__(*a, **k)
 
 
-def _oracle_generate(head, exit_ids, hid, rl, ttype):
-    """OracleValueNet(mode='generate') (value_net.py:134-160) with the candidates' actions kept: hid (bs, W, L, T, d), rl (bs, W) ->
-    (values (n_exit, bs * S), actions (NL, bs, S, 6 A))"""
+def _oracle_values(head, exit_ids, hid, rl, ttype):
+    """OracleValueNet(mode='generate') (value_net.py:134-160): hid (bs, W, L, T, d), rl (bs, W) -> values (n_exit, bs * S)"""
     bs, W, L, T, d = hid.shape
     head.window_size = W
     vn = orc.OracleValueNet(exit_ids, head, 0, W, ttype)
     feats = tuple(hid[:, :, l].reshape(bs * W, T, d) for l in range(L))
     rand = torch.stack([hid[b, t, int(rl[b, t])] for b in range(bs) for t in range(W)])
-    values = vn(feats, mode="generate", rand_layer_feat=rand)
+    return vn(feats, mode="generate", rand_layer_feat=rand)
+
+
+def _oracle_actions(head, exit_ids, hid, rl):
+    """the candidates' actions behind those values (the loop of value_net.py:139-153 with the actions kept): (NL, bs, S, 6 A)"""
+    bs, W, L, T, d = hid.shape
+    head.window_size = W
+    rand = torch.stack([hid[b, t, int(rl[b, t])] for b in range(bs) for t in range(W)])
     acts = []
     for seq_id in range(W // 2 - 1, W - 1):
         prev = rand.reshape(bs, W, T, d)[:, :seq_id]
@@ -71,7 +79,33 @@ def _oracle_generate(head, exit_ids, hid, rl, ttype):
             head.last_action = False
             row.append(a[0].squeeze(1))
         acts.append(torch.stack(row))
-    return values, torch.stack(acts).permute(1, 2, 0, 3)
+    return torch.stack(acts).permute(1, 2, 0, 3)
+
+
+def _oracle_generate(head, exit_ids, hid, rl, ttype):
+    """(values (n_exit, bs * S), actions (NL, bs, S, 6 A))"""
+    return _oracle_values(head, exit_ids, hid, rl, ttype), _oracle_actions(head, exit_ids, hid, rl)
+
+
+COS_MIN_NORM, COS_MAX_LEFT_OUT = 0.1, 0.10
+
+
+def _cosine_comparable(a_ref):
+    """Where the cosine value of a pair of consecutive candidate layers is compared with the oracle's: both fp64 norms of the oracle's actions
+    are >= 0.1.  An action error e turns a unit vector by at most e / |a|, so there the value moves by at most ~ 2 e / 0.1 and the project's
+    gate on values holds for action errors of a twentieth of it; with both actions near zero the direction is rounding noise.  a_ref
+    (NL, bs, S, 6 A) -> bool (n_exit, bs * S)"""
+    n = a_ref.double().norm(dim=-1).flatten(1, 2)
+    return (n[:-1] >= COS_MIN_NORM) & (n[1:] >= COS_MIN_NORM)
+
+
+BS_TINY, W_TINY = (1, 3, 20), (2, 3, 4, 5, 7, 8, 11, 12)
+
+
+def _tiny_case(pool, exit_ids, bs, W):
+    """the committed inputs of test_values_and_actions_vs_oracle_tiny: (hid (bs, W, L, T, d), rand_layers (bs, W))"""
+    idx = torch.tensor([[(7 * b + t) % pool.shape[0] for t in range(W)] for b in range(bs)])
+    return pool[idx], _rand_layers(exit_ids, bs, W, 100 * bs + W)
 
 
 def _rand_layers(exit_ids, bs, W, seed):
@@ -99,6 +133,7 @@ def _tiny_oracle_hidden(n_frames=24):
     return _TINY_HID["h"]
 
 
+_ORACLE_MEMO = {}
 VARIANTS = {"ln_max": {}, "plain": dict(lstm_layernorm=False, mlp_layernorm=False), "avg": dict(pooling="avg"), "ms2": dict(multi_step_action=2)}
 
 
@@ -115,15 +150,19 @@ def test_values_and_actions_vs_oracle_tiny(variant, precision):
     layers = [0] + exit_ids
     A = max(1, cfg.multi_step_action)
     gate, worst = _gate(precision), {}
-    for bs in (1, 3, 20):                                         # 20 windows: more than one sibling engine holds in the per-step loop
-        for W in (2, 4, 8, 12):
-            idx = torch.tensor([[(7 * b + t) % pool.shape[0] for t in range(W)] for b in range(bs)])
-            hid = pool[idx]                                       # (bs, W, L, T, d)
-            rl = _rand_layers(exit_ids, bs, W, 100 * bs + W)
+    pairs = left_out = 0
+    memo = _ORACLE_MEMO.setdefault(variant, {})                   # the oracle does not depend on the engine's precision: once per variant
+    for bs in BS_TINY:                                            # 20 windows: more than one sibling engine holds in the per-step loop
+        for W in W_TINY:                                          # odd W: W/2 - 1 + s and S = W - W/2 round differently; W = 3 starts at seq_id 0
+            hid, rl = _tiny_case(pool, exit_ids, bs, W)           # (bs, W, L, T, d)
             P = _pool(hid, layers, cfg.pooling).cuda()
-            ref = {}
+            if (bs, W) not in memo:
+                memo[bs, W] = (_oracle_actions(head, exit_ids, hid, rl), {t: _oracle_values(head, exit_ids, hid, rl, t) for t in TYPES})
+            a_ref, v_refs = memo[bs, W]
+            cos_ok = _cosine_comparable(a_ref)
+            pairs, left_out = pairs + cos_ok.numel(), left_out + int((~cos_ok).sum())
             for ttype in TYPES:
-                v_ref, a_ref = ref.setdefault(ttype, _oracle_generate(head, exit_ids, hid, rl, ttype))
+                v_ref = v_refs[ttype]
                 v, a = eng.calibrate_values(P, rl, ttype, return_actions=True)
                 assert v.is_cuda and tuple(v.shape) == tuple(v_ref.shape) == (len(exit_ids), bs * (W - W // 2))
                 assert tuple(a.shape) == (len(layers), bs, W - W // 2, 8 * A)
@@ -132,12 +171,15 @@ def test_values_and_actions_vs_oracle_tiny(variant, precision):
                 e64 = float((v.double() - _delta64(a, ttype)).abs().max())
                 ev = float((v - v_ref).abs().max())
                 print(f"{variant} {precision} bs={bs} W={W} {ttype}: |actions-oracle|={ea:.3e} |values-oracle|={ev:.3e} |values-fp64(own actions)|={e64:.3e}")
-                worst[ttype] = max(worst.get(ttype, 0.0), ev)
                 assert ea < gate, (bs, W, ttype, ea)
                 assert e64 < 1e-5, (bs, W, ttype, e64)            # the delta kernel is f32
-                if ttype != "cosine":                             # cosine is ill-conditioned when both actions are near zero: covered by the two above
-                    assert ev < gate, (bs, W, ttype, ev)
-    print(f"{variant} {precision}: worst |values-oracle| {worst}")
+                if ttype == "cosine":                             # compared wherever both oracle actions have a norm >= 0.1 (_cosine_comparable)
+                    ev = float((v - v_ref).abs()[cos_ok].max()) if bool(cos_ok.any()) else 0.0
+                    print(f"{variant} {precision} bs={bs} W={W} cosine: {int((~cos_ok).sum())} of {cos_ok.numel()} pairs left out, |values-oracle|={ev:.3e} on the rest")
+                worst[ttype] = max(worst.get(ttype, 0.0), ev)
+                assert ev < gate, (bs, W, ttype, ev)
+    print(f"{variant} {precision}: worst |values-oracle| {worst}; cosine pairs left out {left_out} of {pairs}")
+    assert left_out <= COS_MAX_LEFT_OUT * pairs, (left_out, pairs)   # the same count on the CPU: test_calibrate_cpu.py
 
 
 # ---- 2. against the reference's recorded output --------------------------------------------------------------------------------------
@@ -216,11 +258,11 @@ def test_fused_vs_per_step_loop_on_device_hidden_states(pooling, precision, monk
 
 
 # ---- 4. chunking and determinism ------------------------------------------------------------------------------------------------------
-def test_chunking_determinism_and_untouched_state():
+def _chunking(bs, W, ttype):
     cfg = _small_towers(deer_tiny())
     eng = DeerEngine(cfg, syn.make_synthetic_state(cfg, 3, bf16_round=True))
     exit_ids = cfg.exit_ids()
-    bs, W, NL = 190, 12, len(exit_ids) + 1
+    NL = len(exit_ids) + 1
     assert bs * (W - 1) > 2048 and (bs // 2) * (W - 1) <= 2048                        # the full call runs in two chunks, each half in one
     P = torch.randn(bs, W, NL, cfg.d_model, generator=torch.Generator().manual_seed(1)).cuda()
     rl = _rand_layers(exit_ids, bs, W, 2)
@@ -228,20 +270,29 @@ def test_chunking_determinism_and_untouched_state():
     eng.c_state.normal_()
     eng.ctl.fill_(7)
     snap = [t.clone() for t in (eng.h_state, eng.c_state, eng.ctl)]
-    v, a = eng.calibrate_values(P, rl, "L2", return_actions=True)
-    v2, a2 = eng.calibrate_values(P, rl, "L2", return_actions=True)
+    v, a = eng.calibrate_values(P, rl, ttype, return_actions=True)
+    v2, a2 = eng.calibrate_values(P, rl, ttype, return_actions=True)
     hb = bs // 2
-    va, aa = eng.calibrate_values(P[:hb], rl[:hb], "L2", return_actions=True)
-    vb, ab = eng.calibrate_values(P[hb:], rl[hb:], "L2", return_actions=True)
+    va, aa = eng.calibrate_values(P[:hb], rl[:hb], ttype, return_actions=True)
+    vb, ab = eng.calibrate_values(P[hb:], rl[hb:], ttype, return_actions=True)
     torch.cuda.synchronize()
     assert bool(torch.isfinite(v).all()) and float(v.abs().max()) > 0
     assert torch.equal(v, v2) and torch.equal(a, a2)                                  # identical calls, identical bits
     assert torch.equal(v, torch.cat([va, vb], dim=1)) and torch.equal(a, torch.cat([aa, ab], dim=1))
     for now, before in zip((eng.h_state, eng.c_state, eng.ctl), snap):
         assert torch.equal(now, before)
-    one = eng.calibrate_values(P[5], rl[5], "L2")                                     # one window (W, NL, d) == its columns of the batch
     S = W - W // 2
-    assert torch.equal(one, v[:, 5 * S:6 * S])
+    for b in (5, bs - 1):                                                             # one window (W, NL, d) == its columns of the batch
+        assert torch.equal(eng.calibrate_values(P[b], rl[b], ttype), v[:, b * S:(b + 1) * S])
+
+
+def test_chunking_determinism_and_untouched_state():
+    _chunking(190, 12, "L2")                                                          # chunks of 186 + 4 windows
+
+
+def test_chunking_odd_window_ragged_last_chunk():
+    """W = 11 (S = 6 of 10 history steps per window): chunks of 204 + 46 windows, the `max` criterion"""
+    _chunking(250, 11, "max")
 
 
 # ---- 5. full size -----------------------------------------------------------------------------------------------------------------------
