@@ -78,7 +78,6 @@ SIGNATURES = {
     "deer_xattn_fused_active": [P, I, P, P, I, I, P, I, I, P, P, L, I, I, I, F, P, P, P],
     "deer_head_pool_active": [P, P, I, I, I, I, P, P, I, I, P, P],
     "deer_ctl_begin_step_map": [P, P, I, P, P],
-    "deer_trunk_layer_persistent": [P, P],
     "deer_layernorm_rows": [P, L, L, I, I, P, P, P, P, L, L, I, F, P],
     "deer_layernorm_rows_multi": [P, L, L, I, I, P, P, I, L, P, L, L, L, I, F, P],
     "deer_resadd_ln": [P, P, I, L, P, P, P, P, P, P, P, I, I, F, P, P],
@@ -104,8 +103,6 @@ SIGNATURES = {
     "deer_head_final_multi": [P, I, I, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P, P, P, I, I, I, P, F, I, I, P, P],
     "deer_head_final_env": [P, I, I, I, P, P, P, P, P, P, P, P, P, I, I, I, P, I, I, I, P, P, P, P, I, I, I, P, F, I, I, P, P],
     "deer_env_exit_write": [P, P, I, P, I, P],
-    "deer_head_fused_granules": [I, I, I, I, I, P],
-    "deer_head_fused": [P, I, I, P],
     "deer_ctl_begin_step": [P, P, I, P],
     "deer_preprocess_frames": [P, I, I, I, I, P, P, P, P, P, P],
     "deer_preprocess_frames_f16": [P, I, I, I, I, P, P, P, P, P, P],
@@ -127,9 +124,7 @@ SIGNATURES = {
     "deer_model_configure_exit": [P, P, I, I, I, I],
     "deer_model_real_num_exit": [P],
     "deer_model_set_compaction": [P, I],
-    "deer_model_set_head_fused": [P, I],
     "deer_model_head_state_changed": [P],
-    "deer_model_set_persistent_layer": [P, I],
     "deer_model_set_env_exit": [P, P, P, I, P],
     "deer_model_set_env_exit_device": [P, P, P, I, P],
     "deer_model_clear_env_exit": [P],
@@ -172,7 +167,7 @@ SIGNATURES = {
     "deer_step_plan_run": [P, I, I, P, P, P, P, P],
     "deer_step_plan_destroy": [P],
 }
-_RESTYPE = {"deer_head_fused_granules": c_long, "deer_hip_arch": c_char_p, "deer_model_arena_bytes": c_long, "deer_model_workspace_bytes": c_long, "deer_preprocess_scratch_bytes": c_long,
+_RESTYPE = {"deer_hip_arch": c_char_p, "deer_model_arena_bytes": c_long, "deer_model_workspace_bytes": c_long, "deer_preprocess_scratch_bytes": c_long,
             "deer_model_scratch_bytes": c_long, "deer_model_destroy": None, "deer_step_plan_destroy": None}
 
 # constants of include/deer_hip.h

@@ -281,7 +281,6 @@ __global__ __launch_bounds__(512) void gemm_skinny_hl_kernel(const bf16_t* __res
   gemm_skinny_hl_body<MT, D, F16>(Ahi, Alo, lda, Wp, part, M, N, K, KR, part_rows, blockIdx.x, blockIdx.y);
 }
 
-#ifndef DEER_BODIES_ONLY
 // Env batch with COMPACTION of exited environments (common.h: CMAP_*): the number of valid rows is read from the device - the active
 // slots x rows_per_env, minus the rows of earlier row blocks - and the workgroup runs the body specialised for that many MFMA row tiles
 // (its own ring depth, DMA counts and waits: exactly the kernel a launch with that M would have run).  A launch costs what its ACTIVE rows
@@ -595,4 +594,3 @@ extern "C" int deer_gemm_skinny_f16(const void* A, int lda, const float* Aslab, 
                                     int M, int N, int K, int splitk, const int* ctl, void* stream) {
   return gemm_skinny<true>(A, lda, Aslab, s_in, slab_stride_in, a_mode, Wp, part, M, N, K, splitk, ctl, stream);
 }
-#endif  // DEER_BODIES_ONLY

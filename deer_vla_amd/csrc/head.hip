@@ -794,7 +794,7 @@ extern "C" int deer_head_fc(const float* src, int src_stride, int in_dim, int pr
   return DEER_OK;
 }
 
-// EXIT_FLAG of an environment, published BEHIND its EXIT_LAYER.  In an env batch the gather of a compaction layer (resadd_body.h) may
+// EXIT_FLAG of an environment, published BEHIND its EXIT_LAYER.  In an env batch the gather of a compaction layer (norm_embed.hip) may
 // run beside this exit check and must never see FLAG = 1 together with a stale LAYER (its workgroups would build different packings):
 // agent-scope release in front of a relaxed agent-scope store of the flag, the reader loads the flags, fences (acquire) and then loads
 // the layers.  One environment: nothing reads the pair concurrently (no compaction) - plain store.
@@ -812,11 +812,9 @@ __device__ __forceinline__ void publish_exit_flag(int* ctl, int B) {
 // One workgroup per environment.  src: [B][src_stride] (the last hidden Linear's output, [2][in_dim] per env).
 // ctl: env b at ctl + b*CTL_WORDS.  State tensors h/c: [L][B][H] (LH = L, sH = H).  action_dbg: [B][64] f32 (64-float stride per
 // environment: pose 6 A | gripper prob A | logit A, A = multi_step_action) or NULL.
-// The work of one environment b as a device function of 512 threads: head_final_kernel runs it one workgroup per environment;
-// head_fused_kernel (below) runs it as the last phase of the one-launch evaluation, with the hidden Linear's output staged in LDS
-// (src0 / src1 then point into LDS) and the new LSTM state taken from the tagged exchange granules (GRAN) instead of h_tmp / c_tmp.
+// The work of one environment b as a device function of 512 threads: head_final_kernel runs it one workgroup per environment.
 // lds: 2 * in_dim + 16 + 64 + 4 floats.  skip_checked: the caller already evaluated head_skip().
-template <typename WT, bool GRAN>
+template <typename WT>
 __device__ __forceinline__ void head_final_body(int b, const float* s0, const float* s1, float* lds, int in_dim, int pro,
                                                 const float* __restrict__ lnw0, const float* __restrict__ lnb0,
                                                 const float* __restrict__ lnw1, const float* __restrict__ lnb1,
@@ -827,8 +825,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
                                                 const float* __restrict__ c_tmp, float* __restrict__ h_state,
                                                 float* __restrict__ c_state, int L, int H, int B,
                                                 float* __restrict__ action_dbg, float eps, int A,
-                                                float* __restrict__ act_ext, const unsigned long long* hgran,
-                                                const unsigned long long* cgran, const int* __restrict__ env_caps) {
+                                                float* __restrict__ act_ext, const int* __restrict__ env_caps) {
   if (head_skip(ctl0, kind, layer, B)) {
     // Every workgroup of a CHECK launch reports exactly once, whatever path it takes: a check nobody needed (stage hold)
     // still tells the host that this segment is over, and a workgroup that starts late may see ALL_EXITED raised by a
@@ -994,7 +991,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
         o8[7] = outv[NA];
         ctl[CTL_EXIT_LAYER] = layer;
         if (!shadow_on) {
-          publish_exit_flag(ctl, B);                      // EXIT_LAYER ordered in front of EXIT_FLAG (resadd_body.h: rowmap_dropped_mask)
+          publish_exit_flag(ctl, B);                      // EXIT_LAYER ordered in front of EXIT_FLAG (norm_embed.hip: rowmap_dropped_mask)
           int* hm = host_mirror(ctl0);
           if (hm != nullptr) {
             for (int i = 0; i < CTL_WORDS; ++i) hm[CTL_WORDS * (1 + b) + i] = ctl[i];
@@ -1082,7 +1079,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
           }
         } else if (commit) {
           for (int i = 0; i < 8; ++i) wf(CTL_OUT_ACTION + i, cur[i]);
-          wi(CTL_EXIT_LAYER, layer);                      // EXIT_LAYER ordered in front of EXIT_FLAG (resadd_body.h: rowmap_dropped_mask)
+          wi(CTL_EXIT_LAYER, layer);                      // EXIT_LAYER ordered in front of EXIT_FLAG (norm_embed.hip: rowmap_dropped_mask)
           publish_exit_flag(ctl, B);
           sctl[CTL_EXIT_FLAG] = 1;
           mirror_i = host_mirror(ctl0) != nullptr ? 1 : 0;
@@ -1117,7 +1114,7 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
   }
   __syncthreads();
   HKT(8);
-  if (!GRAN && *flag && h_state != nullptr && (H & 3) == 0) {   // DeterministicDecoder.hidden_state = h_n (action_head.py:555-556)
+  if (*flag && h_state != nullptr && (H & 3) == 0) {   // DeterministicDecoder.hidden_state = h_n (action_head.py:555-556)
     const int h4 = H >> 2, n4 = L * h4;                   // float4 pieces, two per thread in flight (L * H = 4096: 512 threads, one round)
     for (int i0 = threadIdx.x; i0 < n4; i0 += 2 * blockDim.x) {
       float4 hv[2], cv[2];
@@ -1141,13 +1138,8 @@ __device__ __forceinline__ void head_final_body(int b, const float* s0, const fl
     for (int i = threadIdx.x; i < L * H; i += blockDim.x) {
       const int l = i / H, u = i - l * H;
       const long o = ((long)l * B + b) * H + u;
-      if (GRAN) {     // written by other workgroups of THIS launch: read through the device-coherent granules (every one is complete by now)
-        h_state[o] = __uint_as_float((unsigned)__hip_atomic_load(hgran + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        c_state[o] = __uint_as_float((unsigned)__hip_atomic_load(cgran + o, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-      } else {
-        h_state[o] = h_tmp[o];
-        c_state[o] = c_tmp[o];
-      }
+      h_state[o] = h_tmp[o];
+      c_state[o] = c_tmp[o];
     }
   }
   HKT(9);
@@ -1170,483 +1162,8 @@ __global__ __launch_bounds__(512) void head_final_kernel(const float* __restrict
   const bool grouped = (pro == PRO_GROUP_LN_RELU || pro == PRO_GROUP_RELU);
   const float* s0 = src + (long)b * src_stride;
   const float* s1 = s0 + (grouped ? in_dim : 0);
-  head_final_body<WT, false>(b, s0, s1, lds, in_dim, pro, lnw0, lnb0, lnw1, lnb1, Wa, ba, Wg, bg, ctl0, kind, layer, slot, thresholds, force,
-                             thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, nullptr, nullptr, env_caps);
-}
-
-// ------------------------------------------------------------------------------------------------------------------------------
-// One head evaluation (pool -> L LSTM layers -> hidden Linears -> output Linear + exit gate) as ONE launch (round 5).
-// The eight-launch form above is a chain of dependent latency-bound kernels (64-70 us at one environment, 42-82 MB of weights = 10-16 us
-// of stream): every launch boundary drains the GPU, ramps up again and pays a cold HBM round trip for its weights.  Here G workgroups of
-// 8 waves stay resident for the whole evaluation; wave w owns the SAME rows the separate kernels give a wave (one LSTM hidden unit = its
-// four gate rows, two rows of a hidden Linear) and the vectors that separate the phases - pooled feature, every layer's h, the hidden
-// Linears' outputs: 0.5-2 K floats per environment - travel between workgroups as DATA-TAGGED 8-byte granules {f32 value, tag} written
-// and read with relaxed agent-scope atomics (the guide's hand-off R2: no flag, no fence; a consumer polls the granule itself).  The tag
-// is the number of evaluations the exchange buffer has served (kept beside the error word): nothing is reset between evaluations.  Every phase requests its weight
-// rows BEFORE it gathers its input, so the HBM latency of a phase hides behind the hand-off it has to wait for anyway.
-// The arithmetic per row (k split over the lanes in 512-column steps, in-wave butterfly sums, LayerNorm one wave per row, the output
-// Linear + exit gate = head_final_body) is that of the separate kernels; only control steps with a control block use this form (the
-// window / calibration path and static exits keep the separate kernels).  Every spin is bounded: a timeout raises err[0].
-// Residency: G <= 128 workgroups of 512 threads - they need no particular placement and no other kernel ever waits for them.
-#define HF_SPIN_LIMIT (1 << 22)
-
-#define HF_LN_MAXE 4     // float4 per lane: LayerNorm rows of up to 1024 values (LSTM hidden size, hidden Linears)
-// rows_ln_to_lds in two halves: gamma / beta are requested BEFORE the phase's hand-off wait, the rows are normalised after it (the
-// arithmetic and its order are those of rows_ln_to_lds: one wave per row, in-wave sums)
-struct hf_ln_regs { float4 gw[HF_LN_MAXE], gb[HF_LN_MAXE]; };
-__device__ __forceinline__ void hf_ln_prefetch(hf_ln_regs& r, const float* __restrict__ w, const float* __restrict__ bta, int n) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int e = 0; e < HF_LN_MAXE; ++e) {
-    const int i = (lane + 64 * e) * 4;
-    r.gw[e] = (w != nullptr && i < n) ? *reinterpret_cast<const float4*>(w + i) : float4{0.f, 0.f, 0.f, 0.f};
-    r.gb[e] = (bta != nullptr && i < n) ? *reinterpret_cast<const float4*>(bta + i) : float4{0.f, 0.f, 0.f, 0.f};
-  }
-}
-__device__ __forceinline__ void hf_ln_apply(const hf_ln_regs& r, const float* src, long stride, float* dst, int n, int B, float eps, bool relu) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  for (int b = wave; b < B; b += nw) {
-    const float* s = src + (long)b * stride;
-    float* d = dst + b * n;
-    float4 v[HF_LN_MAXE];
-    float sum = 0.f;
-#pragma unroll
-    for (int e = 0; e < HF_LN_MAXE; ++e) {
-      const int i = (lane + 64 * e) * 4;
-      v[e] = i < n ? *reinterpret_cast<const float4*>(s + i) : float4{0.f, 0.f, 0.f, 0.f};
-      sum += v[e].x + v[e].y + v[e].z + v[e].w;
-    }
-    const float mean = wave_sum(sum) / n;
-    float var = 0.f;
-#pragma unroll
-    for (int e = 0; e < HF_LN_MAXE; ++e)
-      if ((lane + 64 * e) * 4 < n) {
-        const float a = v[e].x - mean, bq = v[e].y - mean, c = v[e].z - mean, dd = v[e].w - mean;
-        var += a * a + bq * bq + c * c + dd * dd;
-      }
-    const float rstd = rsqrtf(wave_sum(var) / n + eps);
-#pragma unroll
-    for (int e = 0; e < HF_LN_MAXE; ++e) {
-      const int i = (lane + 64 * e) * 4;
-      if (i < n) {
-        float4 y;
-        y.x = (v[e].x - mean) * rstd * r.gw[e].x + r.gb[e].x; y.y = (v[e].y - mean) * rstd * r.gw[e].y + r.gb[e].y;
-        y.z = (v[e].z - mean) * rstd * r.gw[e].z + r.gb[e].z; y.w = (v[e].w - mean) * rstd * r.gw[e].w + r.gb[e].w;
-        if (relu) { y.x = fmaxf(y.x, 0.f); y.y = fmaxf(y.y, 0.f); y.z = fmaxf(y.z, 0.f); y.w = fmaxf(y.w, 0.f); }
-        *reinterpret_cast<float4*>(d + i) = y;
-      }
-    }
-  }
-}
-
-__device__ __forceinline__ unsigned long long hf_pack(float v, unsigned tag) {
-  return ((unsigned long long)tag << 32) | (unsigned long long)__float_as_uint(v);
-}
-__device__ __forceinline__ void hf_publish(unsigned long long* g, float v, unsigned tag) {
-  __hip_atomic_store(g, hf_pack(v, tag), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// n tagged granules -> dst (LDS), swept by the first `gw` waves of the workgroup (the others wait at the barrier behind them).  A lane
-// keeps up to 8 requests in flight; granules that have not arrived are requested AGAIN TOGETHER after a short sleep - re-polling them one
-// after the other (the first versions) costs a memory-side round trip per late granule: a freshly loaded copy of the first late one says
-// nothing about the copies of the others, which were loaded before they arrived (profiles/r05_e_head_eval_fused_*: 56-94 us per
-// evaluation against 51-67 for the eight launches).
-__device__ __forceinline__ void hf_gather(const unsigned long long* g, int n, float* dst, unsigned tag, int* err, int gw) {
-  if ((int)threadIdx.x >= 64 * gw) return;
-  const int step = 64 * gw;
-  for (int base = threadIdx.x; base < n; base += step * 8) {
-    unsigned long long v[8];
-    bool ok[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) ok[u] = base + u * step >= n;
-    int spins = 0;
-    while (true) {
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (!ok[u]) v[u] = __hip_atomic_load(g + base + u * step, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      bool pending = false;
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (!ok[u]) {
-          if ((unsigned)(v[u] >> 32) == tag) {
-            ok[u] = true;
-            dst[base + u * step] = __uint_as_float((unsigned)v[u]);
-          } else {
-            pending = true;
-          }
-        }
-      if (!pending) break;
-      if (++spins > HF_SPIN_LIMIT || (spins > 4096 && *(volatile int*)err != 0)) { *err = 1; break; }
-      __builtin_amdgcn_s_sleep(4);
-    }
-  }
-}
-
-// workgroup barrier that orders LDS traffic only: __syncthreads() carries a release fence, which on gfx9 is `s_waitcnt vmcnt(0)` - it would
-// drain the weight rows a phase has just requested and serialise their HBM round trip with the hand-off the phase waits for next
-__device__ __forceinline__ void hf_lds_barrier() {
-  asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-}
-
-template <typename WT, int HBT>
-__global__ __launch_bounds__(512) void head_fused_kernel(deer_head_fused_args a) {
-  const int B = a.B, H = a.H, d = a.d, L = a.L;
-  int* ctl0 = a.ctl;
-  if (head_skip(ctl0, a.kind, a.layer, B)) {
-    if ((int)blockIdx.x < B && a.kind == KIND_CHECK && threadIdx.x == 0) check_done(ctl0, a.slot, B);
-    return;
-  }
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* raw = lds;                          // [B][max_in]: gathered input of the phase
-  float* xs = lds + (long)B * a.max_in;      // [B][max_in] (grouped phases: [2][B][in]): the phase's normalised input
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int TW = gridDim.x * 8, gw = blockIdx.x * 8 + wave;
-  // tag of this evaluation: err[1] counts the evaluations this exchange buffer has served; the workgroup that runs the last phase bumps
-  // it when everything is over (every workgroup that has any work read it before: the last phase waits for all of their results)
-  const unsigned tag = ((const volatile unsigned*)a.err)[1] + 1u;
-  int n_stamp = 0;
-#define HF_STAMP()                                                                     \
-  do {                                                                                 \
-    if (a.trace != nullptr && blockIdx.x == 0 && threadIdx.x == 0 && n_stamp < 64) a.trace[n_stamp] = wall_clock64(); \
-    ++n_stamp;                                                                         \
-  } while (0)
-  HF_STAMP();
-  unsigned long long* gX0 = a.xg;
-  unsigned long long* gH = gX0 + (long)B * d;
-  unsigned long long* gC = gH + (long)L * B * H;
-  unsigned long long* gZ = gC + (long)L * B * H;
-
-  // ---- LSTM layer 0: this wave's four gate rows are requested before anything else ----
-  constexpr int LSTM_PF = 4;
-  const int j0 = gw;                                                  // first hidden unit of this wave (others: j0 + TW, ...)
-  const int jr0 = j0 < H ? j0 : H - 1;
-  typename W8<WT>::reg wi[LSTM_PF][4];
-  {
-    const WT* w_ih = reinterpret_cast<const WT*>(a.w_ih[0]);
-#pragma unroll
-    for (int u = 0; u < LSTM_PF; ++u) {
-      const int k = u * 512 + lane * 8;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) wi[u][q] = k < d ? W8<WT>::load_stream(w_ih + ((long)q * H + jr0) * d + k) : W8<WT>::zero();
-    }
-  }
-  // ---- phase 0: token pool (head_pool_kernel's arithmetic).  One environment: EVERY workgroup pools all d columns for itself - T rows of
-  // d floats from L2, all T loads of a thread in flight - and the first hand-off disappears; env batches spread the pool over the launch ----
-  if (HBT == 1) {
-    for (int i = tid; i < d; i += 512) {
-      const int sl = a.cmap != nullptr ? a.cmap[CMAP_ENV_SLOT] : 0;
-      float acc = 0.f;
-      if (sl >= 0) {
-        const float* x = a.feats + ((long)sl * a.T) * d + i;
-        acc = a.avg ? 0.f : -INFINITY;
-        int n = 0;
-        for (int t0 = 0; t0 < a.T; t0 += 8) {
-          float v[8];
-          bool on[8];
-#pragma unroll
-          for (int u = 0; u < 8; ++u) {
-            on[u] = t0 + u < a.T && (a.key_mask == nullptr || a.key_mask[t0 + u] != 0);
-            v[u] = on[u] ? x[(long)(t0 + u) * d] : 0.f;
-          }
-#pragma unroll
-          for (int u = 0; u < 8; ++u)
-            if (on[u]) { acc = a.avg ? acc + v[u] : fmaxf(acc, v[u]); ++n; }
-        }
-        if (a.avg) acc /= (float)max(n, 1);
-      }
-      xs[i] = acc;
-    }
-  }
-  for (int e = blockIdx.x * 512 + tid; e < B * d && HBT > 1; e += gridDim.x * 512) {
-    const int b = e / d, i = e - b * d;
-    const int sl = a.cmap != nullptr ? a.cmap[CMAP_ENV_SLOT + b] : b;
-    float acc = 0.f;
-    if (sl >= 0) {
-      const float* x = a.feats + ((long)sl * a.T) * d + i;
-      const unsigned char* km = a.key_mask != nullptr ? a.key_mask + b * a.T : nullptr;
-      acc = a.avg ? 0.f : -INFINITY;
-      int n = 0;
-      for (int t = 0; t < a.T; ++t) {
-        if (km != nullptr && km[t] == 0) continue;
-        const float v = x[(long)t * d];
-        acc = a.avg ? acc + v : fmaxf(acc, v);
-        ++n;
-      }
-      if (a.avg) acc /= (float)max(n, 1);
-    }
-    hf_publish(gX0 + e, acc, tag);
-  }
-  HF_STAMP();                                                        // pool done (this workgroup)
-  // ---- LSTM layers ----
-#pragma unroll
-  for (int l = 0; l < 4; ++l) {
-    if (l >= L) break;
-    const int in_dim = l == 0 ? d : H;
-    const WT* w_ih = reinterpret_cast<const WT*>(a.w_ih[l]);
-    if (l > 0) {                                                     // this layer's rows: in flight while the input is gathered
-#pragma unroll
-      for (int u = 0; u < LSTM_PF; ++u) {
-        const int k = u * 512 + lane * 8;
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wi[u][q] = k < in_dim ? W8<WT>::load_stream(w_ih + ((long)q * H + jr0) * in_dim + k) : W8<WT>::zero();
-      }
-    }
-    const bool ln = l > 0 && a.lstm_ln;
-    const float* b_ih = a.b_ih[l];
-    const float* ghh = a.ghh + (long)l * B * 4 * H;
-    const float* c_prev = a.c_prev + (long)l * B * H;
-    // everything else this phase reads from memory is requested before the hand-off wait as well: the LayerNorm affine of the input and
-    // (lane b) the bias / recurrent half / cell state of this wave's first hidden unit
-    hf_ln_regs lnr;
-    if (ln) hf_ln_prefetch(lnr, a.ln_w[l > 0 ? l - 1 : 0], a.ln_b[l > 0 ? l - 1 : 0], in_dim);
-    float pb[4] = {0.f, 0.f, 0.f, 0.f}, pg[4] = {0.f, 0.f, 0.f, 0.f}, pc = 0.f;
-    if (lane < B && j0 < H) {
-      const float* gp = ghh + (long)lane * 4 * H + j0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) { pb[q] = b_ih[q * H + j0]; pg[q] = gp[q * H]; }
-      pc = c_prev[lane * H + j0];
-    }
-    hf_lds_barrier();                                                 // the previous phase's reads of raw / xs are over
-    if (l > 0 || HBT > 1) hf_gather(l == 0 ? gX0 : gH + (long)(l - 1) * B * H, B * in_dim, ln ? raw : xs, tag, a.err, a.gather_waves);
-    hf_lds_barrier();
-    HF_STAMP();                                                      // input gathered
-    if (ln) {
-      hf_ln_apply(lnr, raw, in_dim, xs, in_dim, B, a.eps, false);
-      hf_lds_barrier();
-    }
-    HF_STAMP();                                                      // input normalised
-    for (int j = j0; j < H; j += TW) {
-      float acc[4][HBT];
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int b = 0; b < HBT; ++b) acc[q][b] = 0.f;
-      if (j == j0) {
-#pragma unroll
-        for (int u = 0; u < LSTM_PF; ++u) {
-          const int k = u * 512 + lane * 8;
-          if (k < in_dim) {
-#pragma unroll
-            for (int b = 0; b < HBT; ++b)
-              if (b < B) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) acc[q][b] += W8<WT>::dot(wi[u][q], xs + b * in_dim + k);
-              }
-          }
-        }
-      }
-      for (int k = (j == j0 ? LSTM_PF * 512 : 0) + lane * 8; k < in_dim; k += 512) {
-        typename W8<WT>::reg w[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) w[q] = W8<WT>::load(w_ih + ((long)q * H + j) * in_dim + k);
-#pragma unroll
-        for (int b = 0; b < HBT; ++b)
-          if (b < B) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) acc[q][b] += W8<WT>::dot(w[q], xs + b * in_dim + k);
-          }
-      }
-      float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f;
-#pragma unroll
-      for (int b = 0; b < HBT; ++b)
-        if (b < B) {
-          const float t0 = wave_sum(acc[0][b]), t1 = wave_sum(acc[1][b]), t2 = wave_sum(acc[2][b]), t3 = wave_sum(acc[3][b]);
-          if (lane == b) { gi = t0; gf = t1; gg = t2; go = t3; }
-        }
-      if (lane < B) {
-        const int b = lane;
-        if (j != j0) {
-          const float* gp = ghh + (long)b * 4 * H + j;
-#pragma unroll
-          for (int q = 0; q < 4; ++q) { pb[q] = b_ih[q * H + j]; pg[q] = gp[q * H]; }
-          pc = c_prev[b * H + j];
-        }
-        gi += pb[0] + pg[0]; gf += pb[1] + pg[1]; gg += pb[2] + pg[2]; go += pb[3] + pg[3];
-        const float c2 = sigmoidf_(gf) * pc + sigmoidf_(gi) * tanhf(gg);
-        const float h2 = sigmoidf_(go) * tanhf(c2);
-        const long o = ((long)l * B + b) * H + j;
-        a.c_tmp[o] = c2;
-        a.h_tmp[o] = h2;
-        hf_publish(gC + o, c2, tag);
-        hf_publish(gH + o, h2, tag);
-      }
-    }
-    HF_STAMP();                                                      // layer published (this workgroup)
-  }
-  HF_STAMP();                                                        // LSTM layers published (this workgroup)
-  // ---- hidden Linears of both MLP heads ----
-  const float* lnw_last = L == 4 ? a.ln_w[3] : L == 3 ? a.ln_w[2] : L == 2 ? a.ln_w[1] : a.ln_w[0];   // LayerNorm of the last LSTM layer's output
-  const float* lnb_last = L == 4 ? a.ln_b[3] : L == 3 ? a.ln_b[2] : L == 2 ? a.ln_b[1] : a.ln_b[0];
-  long zoff = 0;
-  int in_dim = H;
-#pragma unroll
-  for (int fi = 0; fi < 3; ++fi) {
-    if (fi >= a.n_fc) break;
-    const int out_dim = a.fc_dim[fi];
-    const int PG = (out_dim + 1) / 2;                                // row pairs per group
-    const int p0 = gw;
-    const bool live0 = p0 < 2 * PG;
-    const int grp0 = live0 ? p0 / PG : 0, n00 = live0 ? 2 * (p0 - grp0 * PG) : 0;
-    const WT* W0 = reinterpret_cast<const WT*>(grp0 ? a.fw[fi][1] : a.fw[fi][0]);
-    typename W8<WT>::reg pw0[2], pw1[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      const int k = u * 512 + lane * 8;
-      pw0[u] = (live0 && k < in_dim) ? W8<WT>::load_stream(W0 + (long)n00 * in_dim + k) : W8<WT>::zero();
-      pw1[u] = (live0 && n00 + 1 < out_dim && k < in_dim) ? W8<WT>::load_stream(W0 + (long)(n00 + 1) * in_dim + k) : W8<WT>::zero();
-    }
-    const float* bb0 = grp0 ? a.fb[fi][1] : a.fb[fi][0];
-    const float pbias0 = live0 ? bb0[n00] : 0.f, pbias1 = (live0 && n00 + 1 < out_dim) ? bb0[n00 + 1] : 0.f;
-    hf_ln_regs lnr0, lnr1;                                           // LayerNorm affine of the phase's input, requested before the wait
-    if (fi == 0) {
-      if (a.lstm_ln) hf_ln_prefetch(lnr0, lnw_last, lnb_last, H);
-    } else if (a.mlp_ln) {
-      hf_ln_prefetch(lnr0, a.fln_w[fi > 0 ? fi - 1 : 0][0], a.fln_b[fi > 0 ? fi - 1 : 0][0], in_dim);
-      hf_ln_prefetch(lnr1, a.fln_w[fi > 0 ? fi - 1 : 0][1], a.fln_b[fi > 0 ? fi - 1 : 0][1], in_dim);
-    }
-    hf_lds_barrier();
-    if (fi == 0) {                                                   // shared input: [LN of] the last LSTM layer's h
-      hf_gather(gH + (long)(L - 1) * B * H, B * H, a.lstm_ln ? raw : xs, tag, a.err, a.gather_waves);
-      hf_lds_barrier();
-      if (a.lstm_ln) {
-        hf_ln_apply(lnr0, raw, H, xs, H, B, a.eps, false);
-        hf_lds_barrier();
-      }
-    } else {                                                         // grouped: x_g = relu([LN_g](z[b][g * in ..])) -> xs[g][b][in]
-      hf_gather(gZ + zoff - (long)B * 2 * in_dim, B * 2 * in_dim, raw, tag, a.err, a.gather_waves);
-      hf_lds_barrier();
-      if (a.mlp_ln) {
-        hf_ln_apply(lnr0, raw, 2 * in_dim, xs, in_dim, B, a.eps, true);
-        hf_ln_apply(lnr1, raw + in_dim, 2 * in_dim, xs + (long)B * in_dim, in_dim, B, a.eps, true);
-      } else {
-#pragma unroll
-        for (int g = 0; g < 2; ++g) rows_to_lds(raw + g * in_dim, 2 * in_dim, xs + (long)g * B * in_dim, in_dim, B, false, nullptr, nullptr, a.eps, true);
-      }
-      hf_lds_barrier();
-    }
-    for (int p = p0; p < 2 * PG; p += TW) {
-      const int grp = p / PG, n0 = 2 * (p - grp * PG);
-      const bool two = n0 + 1 < out_dim;
-      const WT* W = reinterpret_cast<const WT*>(grp ? a.fw[fi][1] : a.fw[fi][0]);
-      const float* bb = grp ? a.fb[fi][1] : a.fb[fi][0];
-      const float* x = xs + (fi == 0 ? 0 : (long)grp * B * in_dim);
-      float a0[HBT], a1[HBT];
-#pragma unroll
-      for (int b = 0; b < HBT; ++b) a0[b] = a1[b] = 0.f;
-      if (p == p0) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          const int k = u * 512 + lane * 8;
-          if (k < in_dim) {
-#pragma unroll
-            for (int b = 0; b < HBT; ++b)
-              if (b < B) {
-                a0[b] += W8<WT>::dot(pw0[u], x + b * in_dim + k);
-                a1[b] += W8<WT>::dot(pw1[u], x + b * in_dim + k);
-              }
-          }
-        }
-      }
-      for (int k = (p == p0 ? 2 * 512 : 0) + lane * 8; k < in_dim; k += 512) {
-        const typename W8<WT>::reg w0 = W8<WT>::load(W + (long)n0 * in_dim + k);
-        const typename W8<WT>::reg w1 = two ? W8<WT>::load(W + (long)(n0 + 1) * in_dim + k) : W8<WT>::zero();
-#pragma unroll
-        for (int b = 0; b < HBT; ++b)
-          if (b < B) {
-            a0[b] += W8<WT>::dot(w0, x + b * in_dim + k);
-            a1[b] += W8<WT>::dot(w1, x + b * in_dim + k);
-          }
-      }
-#pragma unroll
-      for (int b = 0; b < HBT; ++b)
-        if (b < B) {
-          const float s0 = wave_sum(a0[b]), s1 = wave_sum(a1[b]);
-          if (lane == 0) {
-            unsigned long long* z = gZ + zoff + (long)b * 2 * out_dim + (long)grp * out_dim + n0;
-            hf_publish(z, s0 + (p == p0 ? pbias0 : bb[n0]), tag);
-            if (two) hf_publish(z + 1, s1 + (p == p0 ? pbias1 : bb[n0 + 1]), tag);
-          }
-        }
-    }
-    HF_STAMP();                                                      // hidden Linear published (this workgroup)
-    zoff += (long)B * 2 * out_dim;
-    in_dim = out_dim;
-  }
-  // ---- output Linear + exit gate: workgroup b < B serves environment b (head_final_body) ----
-  const int b = blockIdx.x;
-  if (b >= B) return;
-  __syncthreads();
-  int pro;
-  const float *s0, *s1, *lw0, *lb0, *lw1, *lb1;
-  if (a.n_fc == 0) {
-    hf_gather(gH + ((long)(L - 1) * B + b) * H, H, raw, tag, a.err, a.gather_waves);
-    pro = a.lstm_ln ? PRO_LN : PRO_RAW;
-    s0 = s1 = raw;
-    lw0 = lw1 = lnw_last; lb0 = lb1 = lnb_last;
-  } else {
-    hf_gather(gZ + zoff - (long)B * 2 * in_dim + (long)b * 2 * in_dim, 2 * in_dim, raw, tag, a.err, a.gather_waves);
-    pro = a.mlp_ln ? PRO_GROUP_LN_RELU : PRO_GROUP_RELU;
-    s0 = raw; s1 = raw + in_dim;
-    const int nf = a.n_fc;
-    lw0 = nf == 3 ? a.fln_w[2][0] : nf == 2 ? a.fln_w[1][0] : a.fln_w[0][0]; lb0 = nf == 3 ? a.fln_b[2][0] : nf == 2 ? a.fln_b[1][0] : a.fln_b[0][0];
-    lw1 = nf == 3 ? a.fln_w[2][1] : nf == 2 ? a.fln_w[1][1] : a.fln_w[0][1]; lb1 = nf == 3 ? a.fln_b[2][1] : nf == 2 ? a.fln_b[1][1] : a.fln_b[0][1];
-  }
-  __syncthreads();
-  HF_STAMP();                                                        // final input gathered
-  head_final_body<WT, true>(b, s0, s1, xs, in_dim, pro, lw0, lb0, lw1, lb1, reinterpret_cast<const WT*>(a.Wa), a.ba, reinterpret_cast<const WT*>(a.Wg),
-                            a.bg, ctl0, a.kind, a.layer, a.slot, a.thresholds, a.force, a.thr_type, a.leq, a.h_tmp, a.c_tmp, a.h_state, a.c_state, L,
-                            H, B, a.action_dbg, a.eps, a.A, a.act_ext, gH, gC, nullptr);   // shared row only (the model refuses a per-env table here)
-  __syncthreads();
-  HF_STAMP();                                                        // done
-  if (b == 0 && threadIdx.x == 0) ((volatile unsigned*)a.err)[1] = tag;      // one environment: workgroup 0 is the only one that gets here
-}
-
-// granules the exchange buffer of deer_head_fused needs (8 bytes each) for B environments
-extern "C" long deer_head_fused_granules(int B, int d, int H, int L, int n_fc, const int* fc_dim) {
-  long n = (long)B * d + 2L * L * B * H;
-  for (int i = 0; i < n_fc; ++i) n += (long)B * 2 * fc_dim[i];
-  return n;
-}
-
-// One evaluation of the head as one launch.  Arguments: the union of the separate kernels' (deer_head_pool / deer_head_lstm_layer_pre /
-// deer_head_fc / deer_head_final_multi); ghh [L][B][4H] from deer_head_lstm_hh; xg: deer_head_fused_granules() x 8 bytes, zeroed once;
-// err: int32, raised when a hand-off timed out.  Needs a control block (the tag comes from its sequence word), bf16 or f32 weights,
-// L <= 4, n_fc <= 3, B <= 8 and B * 2 * max(d, H, 2 * fc_dim) * 4 <= 150 KB of LDS; returns DEER_ERR_SHAPE otherwise (the caller then
-// uses the separate kernels).
-extern "C" int deer_head_fused(const deer_head_fused_args* args, int w_is_f32, int n_workgroups, void* stream) {
-  if (args == nullptr) return DEER_ERR_SHAPE;
-  deer_head_fused_args a = *args;
-  if (w_is_f32) return DEER_ERR_SHAPE;                    // bf16 weights only: the fp32 / fp16 arithmetics keep the separate kernels
-  // one environment only for now: the 8-environment instantiation (32 accumulators + the prefetched rows + the LayerNorm staging) spills
-  // 273 VGPRs under hipcc - env batches keep the separate kernels
-  if (args->B != 1) return DEER_ERR_SHAPE;
-  if (a.ctl == nullptr || a.xg == nullptr || a.err == nullptr || a.ghh == nullptr || a.B <= 0 || a.B > HB_MAX || a.L <= 0 || a.L > 4 || a.n_fc < 0 ||
-      a.n_fc > 3 || (a.d & 7) || (a.H & 7) || a.d > 2048 || a.H > 1024 || a.kind == KIND_COMMIT || a.A < 1 || a.A > 8)
-    return DEER_ERR_SHAPE;
-  if (a.kind == KIND_CHECK && (a.thresholds == nullptr || a.slot < 0 || a.slot > 61)) return DEER_ERR_SHAPE;
-  int max_in = a.d > a.H ? a.d : a.H;
-  for (int i = 0; i < a.n_fc; ++i) {
-    if ((a.fc_dim[i] & 7) || a.fc_dim[i] > 1024) return DEER_ERR_SHAPE;
-    if (2 * a.fc_dim[i] > max_in) max_in = 2 * a.fc_dim[i];
-  }
-  a.max_in = max_in;
-  static const int gwaves = [] { const char* e = getenv("DEER_HF_GATHER_WAVES"); const int v = e ? atoi(e) : 8; return v < 1 ? 1 : (v > 8 ? 8 : v); }();
-  a.gather_waves = gwaves;
-  const int smem = a.B * 2 * max_in * 4 + 512;
-  if (smem > 150 * 1024) return DEER_ERR_SHAPE;
-  if (n_workgroups < a.B) n_workgroups = a.B;
-  if (n_workgroups > 256) n_workgroups = 256;
-  static std::atomic<bool> attr_set{false};
-  if (!attr_set) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&head_fused_kernel<bf16_t, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess ||
-        false)
-      return DEER_ERR_LAUNCH;
-    attr_set = true;
-  }
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  hipLaunchKernelGGL((head_fused_kernel<bf16_t, 1>), dim3(n_workgroups), dim3(512), smem, st, a);
-  DEER_LAUNCH_CHECK();
-  return DEER_OK;
+  head_final_body<WT>(b, s0, s1, lds, in_dim, pro, lnw0, lnb0, lnw1, lnb1, Wa, ba, Wg, bg, ctl0, kind, layer, slot, thresholds, force,
+                      thr_type, leq, h_tmp, c_tmp, h_state, c_state, L, H, B, action_dbg, eps, A, act_ext, env_caps);
 }
 
 // A = multi_step_action (action_head.py:472-473): Wa has 6 A rows, Wg A rows; A > 1 needs act_ext ([B][4][64] f32: previous /

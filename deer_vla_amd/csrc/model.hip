@@ -182,11 +182,6 @@ struct deer_model {
   std::vector<FcW> fc;
   size_t wa, ba, wg, bg;
   std::vector<HeadW> lw;            // layerwise_exit_eval: per-layer heads in the reference's registration order (lm_exit_modules.0.., lm_head)
-  size_t hf_trace = SIZE_MAX;
-  size_t hf_xg = SIZE_MAX, hf_err = SIZE_MAX;   // one-launch head evaluation (csrc/head.hip: deer_head_fused): exchange granules, error word
-  bool head_fused = false;          // one-launch head evaluation (measured: 65-71 us against 51 for the eight launches - an experiment like the
-                                    // persistent trunk layer; DEER_HEAD_FUSED=1 / deer_model_set_head_fused switch it on)
-  int head_wgs = 128;               // DEER_HEAD_WGS: resident workgroups of the one-launch evaluation
   size_t act_ext = SIZE_MAX;        // multi_step_action > 1: [B][4][64] f32 = previous / committed / ensemble action of 7 A values (+ A gripper logits)
   // workspace
   Layout wl;
@@ -198,7 +193,6 @@ struct deer_model {
   size_t img, vis_x, vis_x_f32, kv_all, ids, key_mask, text_time, x, xn, ao, slab_a, slab_b, qkv_ws, hidden, h_state, c_state, h_tmp,
       c_tmp, h_shadow, c_shadow, pooled, ctl, step_info, thresholds, action_dbg;
   size_t x2, cmap;                  // env batch with compaction of exited environments: second residual-stream buffer, two row maps (common.h CMAP_*)
-  size_t pl_state;                  // csrc/persistent_layer.hip (DEER_PERSISTENT_LAYER=1): 192 barrier words, then the error word
   size_t ln_stats;                  // one-environment trunk (csrc/trunk_r16.hip): q/k LayerNorm moments per 32-column group
   size_t xn_hl, ao_hl, h_hl;        // bf16 hi / lo planes of the trunk activations (env batches > kHlMinRows rows: deer_gemm_skinny_hl)
   long hl_plane_d, hl_plane_h;      // elements per plane: rows * d, rows * max_n
@@ -212,7 +206,6 @@ struct deer_model {
   int cfg_max_layer = 0;            // the cap deer_model_configure_exit derived (ctl_max_layer while no per-environment table is active)
   size_t env_exit = SIZE_MAX;       // per-environment operating points (common.h ENV_EXIT_*): threshold row + layer cap of every environment
   bool env_exit_on = false;         // deer_model_set_env_exit*: exit checks read env_exit; ctl_max_layer = the largest cap
-  bool persistent_layer = false;    // N1 experiment: one launch per trunk layer (DEER_PERSISTENT_LAYER=1 / deer_model_set_persistent_layer)
   size_t ghh = 0;
   void* seq_scratch = nullptr;      // deer_head_sequence: device scratch of the window-mode head, allocated at first use and grown on demand
   size_t seq_bytes = 0;
@@ -597,7 +590,6 @@ void build_workspace(deer_model* m) {
   m->h_hl = m->wl.add((size_t)2 * m->hl_plane_h * 2);
   m->x2 = m->wl.add((size_t)T * d * 4);
   m->cmap = named(m, "cmap", (size_t)2 * CMAP_WORDS * 4);
-  m->pl_state = named(m, "pl_state", (size_t)(16 * 12 + 16 + 64 * 64) * 4);     // persistent-layer experiment: barrier words + error word
   m->ln_stats = m->wl.add((size_t)(3 * d / 32 + 1) * 16 * 2 * 4);
   m->hidden = named(m, "hidden", (size_t)c.n_layers * T * d * 4);
   const size_t st = (size_t)m->Lh * B * m->H * 4;
@@ -621,9 +613,6 @@ void build_workspace(deer_model* m) {
   // familiar [pose6, prob, logit])
   m->action_dbg = named(m, "action_dbg", (size_t)B * 64 * 4);
   m->act_ext = named(m, "act_ext", (size_t)B * 4 * 64 * 4);
-  m->hf_xg = named(m, "head_fused_xg", (size_t)deer_head_fused_granules(B, d, m->H, m->Lh, m->n_fc, m->fc_dims) * 8);
-  m->hf_err = named(m, "head_fused_err", 256);
-  m->hf_trace = named(m, "head_fused_trace", 64 * 8);
   if (!m->lw.empty()) {                                                // per-layer heads: own LSTM state, ONE dense block
     // host view: [head][2 (h, c)][Lh][B][H], heads in registration order (dense whatever st is: st is a multiple of 32 bytes, H % 8 == 0)
     const size_t base = m->wl.add(2 * st * m->lw.size());
@@ -1083,32 +1072,6 @@ int llm_layer_r16(deer_model* m, int i, int T, bool use_mask, bool pending_in, b
   }
   int S;
   long stride;
-  // N1 experiment (csrc/persistent_layer.hip): the whole layer as ONE persistent launch - same device functions, same order, bit-identical
-  // results, SLOWER; never the default (a persistent launch needs all of its workgroups resident: one engine per GPU)
-  if (m->persistent_layer && m->env_exit_on) return DEER_ERR_SHAPE;   // the experiment knows the shared operating point only
-  if (m->persistent_layer && !m->f16 && L.has_xa && c.xattn_ff_mult == 4 && c.mlp_ratio == 4) {
-    const XattnW& X = L.xa;
-    deer_trunk_layer_args a{};
-    a.T = T; a.d = d; a.xinner = xin; a.heads = c.xattn_heads; a.n_heads = c.n_heads; a.ffw = (int)ffw; a.n_kv = m->n_media; a.n_per_media = m->n_media;
-    a.ld_kv = m->n_xattn * 2 * xin; a.NS = ((d >> 4) + 31) / 32; a.pending_s = pending_in ? pend.S : 0; a.qk_ln = c.attn_qk_ln ? 1 : 0;
-    a.s_w2 = deer_skinny_hl_splitk(T, d, (int)ffw); a.s_wo = deer_skinny_hl_splitk(T, d, d); a.s_down = a.s_w2;
-    if (pending_in && (pend.S != a.s_down || pend.stride != 16L * d)) return DEER_ERR_SHAPE;
-    a.eps = kEps; a.xattn_scale = 1.0f / sqrtf((float)c.xattn_dim_head); a.alibi_bias_max = (float)c.alibi_bias_max;
-    a.x = m->Wk<float>(m->x); a.slab_a = slab_a; a.qkv = qkv; a.stats = m->Wk<float>(m->ln_stats); a.prev_hidden = prev_hidden;
-    a.hidden_out = finalize ? m->Wk<float>(m->hidden) + (size_t)i * rows_cap * d : nullptr;
-    a.xn_hi = const_cast<bf16_t*>(xh); a.xn_lo = const_cast<bf16_t*>(xh) + m->hl_plane_d; a.h_hi = hh; a.h_lo = hl; a.ao_hi = aoh; a.ao_lo = aol;
-    a.kv = m->Wk<char>(m->kv_all) + (size_t)X.kv_index * 2 * xin * 2; a.text_time = m->Wk<int>(m->text_time);
-    a.key_mask = use_mask ? (m->mask_override ? m->mask_override : m->Wk<unsigned char>(m->key_mask)) : nullptr;
-    a.x_nw = m->A<float>(X.nw); a.x_nb = m->A<float>(X.nb); a.x_ag = m->A<float>(X.ag); a.x_fnw = m->A<float>(X.fnw); a.x_fnb = m->A<float>(X.fnb);
-    a.x_fg = m->A<float>(X.fg); a.ln1w = m->A<float>(L.ln1w); a.ln1b = m->loaded(L.ln1b_name) ? m->A<float>(L.ln1b) : nullptr;
-    a.ln2w = m->A<float>(L.ln2w); a.ln2b = m->loaded(L.ln2b_name) ? m->A<float>(L.ln2b) : nullptr; a.qlnw = m->A<float>(L.qlnw); a.klnw = m->A<float>(L.klnw);
-    a.x_wq = m->A<void>(X.wq); a.x_wo = m->A<void>(X.wo); a.x_w1 = m->A<void>(X.w1); a.x_w2 = m->A<void>(X.w2);
-    a.wqkv = m->A<void>(L.wqkv); a.wo = m->A<void>(L.wo); a.wup = m->A<void>(L.wup); a.wdown = m->A<void>(L.wdown);
-    a.barrier = m->Wk<unsigned>(m->pl_state); a.error = m->Wk<int>(m->pl_state) + 16 * 12;
-    a.trace = i < 64 ? a.error + 16 + 64 * i : nullptr;   // per layer: who arrived last at every barrier, and when (tools/persistent_layer_check.py)
-    Bracket b(m, "deer_trunk_layer_persistent", 2.0 * T * (2.0 * d * xin + 8.0 * d * d + 12.0 * d * d), 2.0 * (2.0 * d * xin + 20.0 * d * d), st);
-    return deer_trunk_layer_persistent(&a, st);
-  }
   if (L.has_xa) {   // gated x-attn (helpers.py:260-279)
     const XattnW& X = L.xa;
     DEER_TRY(resadd_packed(m, T, pp, m->A<float>(X.nw), m->A<float>(X.nb), prev_hidden, ctl, st));
@@ -1319,40 +1282,9 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
   const bool feats_default = feats == nullptr;
   if (feats == nullptr) feats = m->Wk<float>(m->hidden) + (size_t)layer * rows_cap * d;     // [B*T, d]: env b owns rows b*T .. b*T+T-1
   const unsigned char* km = use_mask ? (m->mask_override ? m->mask_override : m->Wk<unsigned char>(m->key_mask)) : nullptr;
-  // a per-environment table: the one-launch evaluation and an explicit threshold row (deer_llm_early_exit) only know the shared row
+  // a per-environment table: an explicit threshold row (deer_llm_early_exit) only knows the shared row
   const bool env_thr = m->env_exit_on && head == 0 && kind == DEER_KIND_CHECK && !no_ctl_final;
-  if (env_thr && (m->head_fused || m->thr_override != nullptr)) return DEER_ERR_SHAPE;
-  // ---- control steps of one environment: the whole evaluation as ONE launch (csrc/head.hip: head_fused_kernel) ----
-  if (m->head_fused && !m->f16 && head == 0 && use_ctl && !no_ctl_final && feats_default && kind != DEER_KIND_COMMIT && B == 1 && !c.precision && !c.use_state &&
-      m->head_pre && m->ghh_valid && m->Lh <= 4 && m->n_fc <= 3 && d <= 2048 && H <= 1024) {
-    deer_head_fused_args a{};
-    a.feats = feats; a.T = T; a.d = d; a.avg = c.pooling_avg; a.key_mask = km;
-    a.cmap = compact_active(m, B * T) ? m->Wk<int>(m->cmap) + cmap_parity(m, layer) * CMAP_WORDS : nullptr;
-    a.B = B; a.H = H; a.L = m->Lh; a.n_fc = m->n_fc; a.lstm_ln = c.lstm_layernorm; a.mlp_ln = c.mlp_layernorm;
-    for (int i = 0; i < 3; ++i) a.fc_dim[i] = m->fc_dims[i];
-    for (int l = 0; l < m->Lh; ++l) {
-      a.w_ih[l] = m->A<void>(m->lstm[l].wih); a.b_ih[l] = m->A<float>(m->lstm[l].bih);
-      a.ln_w[l] = c.lstm_layernorm ? m->A<float>(m->lstm[l].lnw) : nullptr; a.ln_b[l] = c.lstm_layernorm ? m->A<float>(m->lstm[l].lnb) : nullptr;
-    }
-    a.ghh = m->Wk<float>(m->ghh); a.c_prev = m->Wk<float>(m->c_state); a.h_tmp = m->Wk<float>(m->h_tmp); a.c_tmp = m->Wk<float>(m->c_tmp);
-    for (int i = 0; i < m->n_fc; ++i)
-      for (int g = 0; g < 2; ++g) {
-        a.fw[i][g] = m->A<void>(m->fc[i].w[g]); a.fb[i][g] = m->A<float>(m->fc[i].b[g]);
-        a.fln_w[i][g] = c.mlp_layernorm ? m->A<float>(m->fc[i].lnw[g]) : nullptr; a.fln_b[i][g] = c.mlp_layernorm ? m->A<float>(m->fc[i].lnb[g]) : nullptr;
-      }
-    a.Wa = m->A<void>(m->wa); a.ba = m->A<float>(m->ba); a.Wg = m->A<void>(m->wg); a.bg = m->A<float>(m->bg);
-    a.ctl = m->Wk<int>(m->ctl); a.kind = kind; a.layer = layer; a.slot = slot;
-    a.thresholds = m->thr_override ? m->thr_override : m->Wk<float>(m->thresholds);
-    a.force = force ? 1 : 0; a.thr_type = m->thr_type; a.leq = m->leq;
-    a.h_state = m->Wk<float>(shadow ? m->h_shadow : m->h_state); a.c_state = m->Wk<float>(shadow ? m->c_shadow : m->c_state);
-    a.action_dbg = m->Wk<float>(m->action_dbg); a.eps = kEps; a.A = std::max(1, c.multi_step_action); a.act_ext = m->Wk<float>(m->act_ext);
-    a.xg = m->Wk<unsigned long long>(m->hf_xg); a.err = m->Wk<int>(m->hf_err);
-    static const bool hf_trace_on = [] { const char* e = getenv("DEER_HF_TRACE"); return e != nullptr && e[0] == '1'; }();
-    a.trace = hf_trace_on ? m->Wk<unsigned long long>(m->hf_trace) : nullptr;
-    Bracket b(m, "deer_head_fused", 0, 2.0 * (4.0 * H * (d + (m->Lh - 1.0) * H)), st);
-    const int rc = deer_head_fused(&a, 0, m->head_wgs, st);
-    if (rc != DEER_ERR_SHAPE) return rc;                       // DEER_ERR_SHAPE: a shape the one-launch form does not take -> separate kernels
-  }
+  if (env_thr && m->thr_override != nullptr) return DEER_ERR_SHAPE;
   float* pooled = m->Wk<float>(m->pooled);
   {
     Bracket b(m, "deer_head_pool", 0, 0, st);
@@ -1506,6 +1438,17 @@ int vision(deer_model* m, const VisionWS& ws, int part, bool with_kv, void* st) 
   return DEER_OK;
 }
 
+// experiments that were removed: a knob that silently does nothing would hide that, so creation refuses it
+bool retired_knob_set() {
+  for (const char* name : {"DEER_HEAD_FUSED", "DEER_PERSISTENT_LAYER", "DEER_ONE_GRAPH"}) {
+    const char* e = getenv(name);
+    if (e == nullptr || e[0] == 0 || strcmp(e, "0") == 0) continue;
+    fprintf(stderr, "deer_model_create: %s is a retired experiment, see DESIGN.md\n", name);
+    return true;
+  }
+  return false;
+}
+
 }  // namespace
 
 // ====================================================================================================================
@@ -1513,6 +1456,7 @@ extern "C" {
 
 int deer_model_create(const deer_config* cfg, deer_model** out) {
   if (cfg == nullptr || out == nullptr) return DEER_ERR_SHAPE;
+  if (retired_knob_set()) return DEER_ERR_SHAPE;
   const deer_config& c = *cfg;
   if (c.n_envs < 1 || c.n_envs > DEER_MAX_ENVS || c.max_text_len < 1 || c.n_layers < 1 || c.vit_layers < 1 || c.perc_depth < 1) return DEER_ERR_SHAPE;
   if (c.image_size % c.patch_size) return DEER_ERR_SHAPE;
@@ -1553,16 +1497,7 @@ int deer_model_create(const deer_config* cfg, deer_model** out) {
   m->ctl_max_layer = m->cfg_max_layer = m->exit_ids.back();
   if (const char* e = getenv("DEER_COMPACT")) m->compact = e[0] != '0';
   if (const char* e = getenv("DEER_HEAD_PRE")) m->head_pre = e[0] != '0';
-  if (const char* e = getenv("DEER_HEAD_FUSED")) m->head_fused = e[0] != '0';
-  if (const char* e = getenv("DEER_HEAD_WGS")) m->head_wgs = std::max(1, std::min(256, atoi(e)));
-  if (const char* e = getenv("DEER_PERSISTENT_LAYER")) m->persistent_layer = e[0] == '1';
   *out = m;
-  return DEER_OK;
-}
-
-int deer_model_set_persistent_layer(deer_model* m, int on) {
-  if (m == nullptr || (on && m->env_exit_on)) return DEER_ERR_SHAPE;
-  m->persistent_layer = on != 0;  // takes effect for pieces enqueued / captured from now on; one engine per GPU only (see csrc/persistent_layer.hip)
   return DEER_OK;
 }
 
@@ -1570,13 +1505,6 @@ int deer_model_set_persistent_layer(deer_model* m, int on) {
 // to the fused LSTM kernel, which reads h_state itself
 int deer_model_head_state_changed(deer_model* m) {
   m->ghh_valid = false;
-  return DEER_OK;
-}
-
-// control steps of one environment: the head evaluation as one launch (DEER_HEAD_FUSED=1; off by default: measured slower) or as the eight separate kernels
-int deer_model_set_head_fused(deer_model* m, int on) {
-  if (m == nullptr || (on && m->env_exit_on)) return DEER_ERR_SHAPE;
-  m->head_fused = on != 0;   // takes effect for pieces enqueued / captured from now on
   return DEER_OK;
 }
 
@@ -1719,7 +1647,6 @@ int deer_model_configure_exit(deer_model* m, const int* exit_ids, int n_exit, in
 // derives, min(max_layer - 1, last exit)); the plan runs to the largest cap
 static int env_exit_set(deer_model* m, const float* rows, int rows_on_device, const int* caps, int n_envs, void* stream) {
   if (m == nullptr || m->ws == nullptr || rows == nullptr || caps == nullptr || n_envs != m->B) return DEER_ERR_SHAPE;
-  if (m->head_fused || m->persistent_layer) return DEER_ERR_SHAPE;           // the experiments read the shared row only
   int cmax = -1, eff[DEER_MAX_ENVS];
   for (int b = 0; b < n_envs; ++b) {
     eff[b] = std::min(caps[b], m->exit_ids.back());

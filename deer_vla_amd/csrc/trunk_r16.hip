@@ -32,7 +32,7 @@ enum { TR_EPI_F32 = 0, TR_EPI_GELU_PLANES = 1, TR_EPI_F32_STATS = 2 };
 // workgroup = 16 CT output columns (CT MFMA column tiles), 8 waves x KS k-tiles of 32 (K = 256 * KS): CT = 2 up to K = 2048, CT = 1 at
 // K = 4096 (MPT-7B, round 5: 16 k-tiles per wave - the weight + activation fragments of TWO column tiles would not fit the registers;
 // the workgroup streams the same 128 KB of weights either way)
-// (bodies are device functions taking the LOGICAL workgroup index: csrc/persistent_layer.hip runs them as phases of one launch)
+// (bodies are device functions taking the LOGICAL workgroup index)
 template <int KS, int EPI, int CT = 2, bool F16 = false>
 __device__ __forceinline__ void trunk_wide_gemm_body(const bf16_t* __restrict__ Ahi, const bf16_t* __restrict__ Alo,
                                                      const bf16_t* __restrict__ Wp, float* __restrict__ out_f32,
@@ -115,7 +115,6 @@ __global__ __launch_bounds__(64 * TR_NW) void trunk_wide_gemm_kernel(const bf16_
   trunk_wide_gemm_body<KS, EPI, CT, F16>(Ahi, Alo, Wp, out_f32, out_hi, out_lo, ldo, stats, T, blockIdx.x, opart);
 }
 
-#ifndef DEER_BODIES_ONLY
 // y = A W^T for the wide bias-free Linears at <= 16 rows.  a_hi / a_lo: the activation as bf16 planes in MFMA-fragment order
 // [K/32][64 lanes][8] (lane = 16 * (k % 32 / 8) + row; written by deer_resadd_ln_packed), Wp packed [N/16][K/32][64][8].
 // epi: 0 = out_f32 [T][ldo]; 1 = exact GELU -> ROW-MAJOR bf16 hi / lo planes [T][ldo]; 2 = out_f32 + stats [N/32][16][2] (mean, centred
@@ -159,7 +158,6 @@ extern "C" int deer_trunk_wide_gemm_f16(const void* a_hi, const void* a_lo, cons
                                         void* out_lo, int ldo, float* stats, int T, const int* ctl, void* stream) {   // fp16 weights / planes (round 6)
   return trunk_wide_gemm<true>(a_hi, a_lo, Wp, N, K, epi, out_f32, out_hi, out_lo, ldo, stats, T, ctl, stream);
 }
-#endif  // DEER_BODIES_ONLY
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // deer_trunk_mpt_attn: MPT attention core on final f32 q|k|v [T][3d]: q/k LayerNorm over the FULL d_model from the
@@ -168,7 +166,7 @@ extern "C" int deer_trunk_wide_gemm_f16(const void* a_hi, const void* a_lo, cons
 // ---------------------------------------------------------------------------------------------------------------------------
 #define TM_MAXT 16
 #define TM_LDS_FLOATS (3 * TM_MAXT * 132 + TM_MAXT * (TM_MAXT + 1) + 2 * TM_MAXT * 2)
-#if defined(DEER_KTRACE) && !defined(DEER_BODIES_ONLY)
+#ifdef DEER_KTRACE
 KT_DEFINE(mpt_attn)
 #define MKT(slot) KT(mpt_attn, h == 0, slot)
 #else
@@ -179,7 +177,7 @@ KT_DEFINE(mpt_attn)
 // instead of two), the moments are combined in one pass over registers, and a query row is ONE WAVE from scores to output - lane =
 // (key j = lane / 4, quarter of the head dimension): partial dot products meet by two xor-shuffles, the softmax runs over the 16
 // key groups by four more, P V takes the probabilities from lane registers (v_readlane) - two barriers instead of five.
-template <int NT, bool F16 = false>     // threads of the workgroup (256; 512 as a phase of the persistent layer); F16: fp16 hi / lo output planes
+template <int NT, bool F16 = false>     // threads of the workgroup (256); F16: fp16 hi / lo output planes
 __device__ __forceinline__ void trunk_mpt_attn_body(const float* __restrict__ qkv, const float* __restrict__ stats, int d_model, int hd,
                                                     const float* __restrict__ q_ln_w, const float* __restrict__ k_ln_w, float eps,
                                                     const unsigned char* __restrict__ key_mask, float alibi_slope_base, int n_heads,
@@ -345,7 +343,6 @@ __device__ __forceinline__ void trunk_mpt_attn_body(const float* __restrict__ qk
   MKT(13);
 }
 
-#ifndef DEER_BODIES_ONLY
 template <bool F16>
 __global__ __launch_bounds__(1024) void trunk_mpt_attn_kernel(const float* __restrict__ qkv, const float* __restrict__ stats, int d_model, int hd,
                                                              const float* __restrict__ q_ln_w, const float* __restrict__ k_ln_w, float eps,
@@ -380,4 +377,3 @@ extern "C" int deer_trunk_mpt_attn_f16(const float* qkv, const float* stats, int
                                        void* stream) {   // fp16 hi / lo output planes (round 6)
   return trunk_mpt_attn<true>(qkv, stats, d_model, n_heads, q_ln_w, k_ln_w, eps, key_mask, alibi_bias_max, out_hi, out_lo, ldo, T, ctl, stream);
 }
-#endif  // DEER_BODIES_ONLY

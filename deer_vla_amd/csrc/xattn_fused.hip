@@ -21,7 +21,7 @@ typedef __attribute__((address_space(3))) xf_s16x4_t xf_lds_s16x4_t;
 #define XF_HD 64
 #define XF_KP 72           // K rows: 64 + 8 bf16
 #define XF_MAXKV 128
-#if defined(DEER_KTRACE) && !defined(DEER_BODIES_ONLY)
+#ifdef DEER_KTRACE
 KT_DEFINE(xattn)
 #define XKT(slot) KT(xattn, bx == 0 && by == 0, slot)
 #else
@@ -298,7 +298,6 @@ __global__ __launch_bounds__(64 * XF_NW) void xattn_fused_kernel(const float* __
                                blockIdx.x, blockIdx.y);
 }
 
-#ifndef DEER_BODIES_ONLY
 // xn: f32 [batch*T, d] = LN(x) of the block's attention branch; Wq_p / Wo_p: to_q [inner, d] and to_out [d, inner] in the packed
 // layout of deer_pack_weight_mfma16; kv: bf16 [batch*n_kv, ldkv] (k of head h at column h*64, v at inner + h*64); out: f32
 // [heads][slab_stride] with slab_stride >= batch*T*d - slab h holds head h's contribution to all rows.  T <= 32, n_kv <= 128.
@@ -396,4 +395,3 @@ static int launch_xattn_fused(const float* xn, const void* x_lo_packed, int d, c
   DEER_LAUNCH_CHECK();
   return DEER_OK;
 }
-#endif  // DEER_BODIES_ONLY

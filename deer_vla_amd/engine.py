@@ -175,10 +175,6 @@ class DeerEngine:
         self._siblings: Dict[int, "DeerEngine"] = {}
         self._graphs: Dict[tuple, torch.cuda.CUDAGraph] = {}
         self.segmented = segmented and self.product         # dynamic steps fed in per-layer graph pieces (see _step_segmented)
-        # DEER_ONE_GRAPH=1: dynamic steps as ONE graph with branches - no host on the decision path at all, but every kernel behind
-        # the exit still launches and returns at entry (see _step_one_graph; measured slower: 242 vs 352 steps/s at one
-        # environment, 778 vs 862 at eight)
-        self._one_graph = os.environ.get("DEER_ONE_GRAPH") == "1"
         self._side_stream = torch.cuda.Stream(device=self.dev)
         self._drain_events: Dict[torch.cuda.Stream, torch.cuda.Event] = {}
         self._plans = []                                                   # native step plans (own HIP events): freed with the graphs
@@ -341,49 +337,6 @@ class DeerEngine:
         if self._graphs:
             torch.cuda.synchronize(self.dev)
         self._drop_graphs()
-
-    def set_head_fused(self, on: bool):
-        """One-environment control steps: every head evaluation (pseudo action / exit check) as ONE launch (csrc/head.hip:
-        head_fused_kernel) instead of the eight separate kernels (default).  Same arithmetic per row (tests/test_engine_parity.py);
-        measured SLOWER (65-71 us against 51 us per evaluation: every hand-off between resident workgroups costs 6-8 us, a kernel
-        boundary 1.4 us + ramp) - an experiment like the persistent trunk layer, kept switchable (DEER_HEAD_FUSED=1)."""
-        abi.check(self.lib.deer_model_set_head_fused(self._h, 1 if on else 0), "deer_model_set_head_fused")
-        if self._graphs:
-            torch.cuda.synchronize(self.dev)
-        self._drop_graphs()
-
-    def head_fused_error(self) -> int:
-        """1 if a hand-off inside a one-launch head evaluation timed out (the step then ends without a verdict)"""
-        return int(self._buf("head_fused_err").view(torch.int32)[0].item())
-
-    def set_persistent_layer(self, on: bool):
-        """N1 experiment (csrc/persistent_layer.hip): one persistent launch per trunk layer of a one-environment step.  Bit-identical to
-        the twelve-launch layer and slower; needs ALL of its 256 workgroups resident, so only one engine per GPU may use it at a time."""
-        if on and (self._siblings or self.B > 1):
-            # the persistent launch needs ALL of its 256 workgroups resident at once and ignores ALL_EXITED: engines that run beside it on
-            # the same GPU (sibling engines of a window / env batches in flight) cannot promise that (ADVICE r4)
-            raise abi.DeerHipError("set_persistent_layer(True): a stand-alone one-environment engine only (no sibling engines, no env batch)")
-        abi.check(self.lib.deer_model_set_persistent_layer(self._h, 1 if on else 0), "deer_model_set_persistent_layer")
-        self._persistent_on = bool(on)
-        torch.cuda.synchronize(self.dev)
-        self._drop_graphs()
-        self._buf("pl_state").view(torch.int32)[:16 * 12 + 16].zero_()   # barrier counters (cumulative over launches) + error words
-
-    def persistent_layer_error(self) -> int:
-        """barrier number that timed out in a persistent layer launch (0 = none)"""
-        return int(self._buf("pl_state").view(torch.int32)[16 * 12].item())
-
-    def persistent_layer_trace(self, clear: bool = False):
-        """int32 [64 layers][16 barriers][clock lo, clock hi (100 MHz), last workgroup to arrive, timeouts]; row 0 = entry of workgroup 0"""
-        t = self._buf("pl_state").view(torch.int32)[16 * 12 + 16:16 * 12 + 16 + 64 * 64].view(64, 16, 4)
-        out = t.cpu()
-        if clear:
-            t.zero_()
-        return out
-
-    def persistent_layer_error_detail(self):
-        """[epoch, workgroup, generation word, top counter, 8 group counters] recorded by the first barrier that timed out"""
-        return [int(v) for v in self._buf("pl_state").view(torch.int32)[16 * 12:16 * 12 + 12].tolist()]
 
     def configure_exit(self, exit_ids: Sequence[int], max_layer: int, steps_per_stage: int = 1):
         """``ExitController.__init__`` (value_net.py:164-173): max_layer = min(max_layer-1, last exit)."""
@@ -739,8 +692,6 @@ class DeerEngine:
             si = self._si_np
             si[0], si[1] = hold, self._seq
             self.cur_step += 1
-            if seg_mode and self._one_graph:
-                return self._step_one_graph(T, use_mask)
             return self._step_segmented(T, use_mask) if seg_mode else self._step_static_pieces(T, use_mask, exit_id)
         si = self.step_info_host[self._seq & 7]
         si[0], si[1], si[2], si[3] = hold, self._seq, 0, 0
@@ -853,64 +804,6 @@ class DeerEngine:
             self.last_stage_ms = {"vision": ev[0].elapsed_time(ev[1]), "llm_and_exit_checks": ev[1].elapsed_time(ev[2])}
         return self.read_result()
 
-    def _step_one_graph(self, T, use_mask):
-        """Dynamic step as ONE graph with parallel branches (opt-in, DEER_ONE_GRAPH=1): both vision chains, the trunk layers and -
-        forked off after each exit layer - the head evaluations.  The host replays it and reads the verdict; nothing on the host
-        sits between an exit decision and the end of the step.  Kernels behind the exit return at entry (~1.6 us each, ~150
-        launches after an exit at layer 1), which is why the host-fed pieces of _step_segmented are the default: measured on
-        MI355X 242 vs 352 steps/s with one environment and 778 vs 862 with eight."""
-        key = (T, use_mask, "one_graph")
-        g = self._graphs.get(key)
-        main_st = torch.cuda.current_stream()
-        if g is None:
-            self.hold_dev.copy_(self.step_info_pinned, non_blocking=True)
-            self._enqueue_step(T, use_mask, None)                 # eager warm-up of the whole step - a real step
-            main_st.synchronize()
-            plan = self.dynamic_plan()
-            side = self._side_stream
-            keep = []
-
-            def fork(src, dst):
-                e = torch.cuda.Event()
-                e.record(src)
-                dst.wait_event(e)
-                keep.append(e)
-
-            g = torch.cuda.CUDAGraph()
-            with _capture(g):
-                cap = torch.cuda.current_stream()
-                fork(cap, side)
-                with torch.cuda.stream(side):
-                    for c in range(1, self.n_chains):
-                        self._enqueue_chain(c, "head")
-                        self._enqueue_chain(c, "tail")
-                self._enqueue_chain(0, "head")
-                self._enqueue_chain(0, "tail")
-                fork(side, cap)
-                self._enqueue_media_kv()
-                for i, need_pseudo, is_exit, _ in plan:
-                    if self.B > 1 and i >= 2 and plan[i - 2][2]:
-                        fork(side, cap)                           # compaction layer: needs the verdict of the exit check of layer i - 2
-                    self.enqueue_dynamic_main(T, use_mask, i)
-                    if need_pseudo or is_exit:
-                        fork(cap, side)
-                        with torch.cuda.stream(side):
-                            self.enqueue_dynamic_heads(T, i, use_mask=use_mask)
-                fork(side, cap)
-            self._graphs[key] = g
-            self._graphs[(key, "events")] = keep
-            self.ctl_host.copy_(self.ctl, non_blocking=True)
-            if self.A > 1:
-                self.act_ext_host.copy_(self.act_ext, non_blocking=True)
-            main_st.synchronize()
-            return self.read_result()
-        g.replay()
-        self.ctl_host.copy_(self.ctl, non_blocking=True)
-        if self.A > 1:
-            self.act_ext_host.copy_(self.act_ext, non_blocking=True)
-        main_st.synchronize()
-        return self.read_result()
-
     def _drop_graphs(self):
         """forget every captured graph (exit configuration changed) together with the native plans built over them"""
         for pl in self._plans:
@@ -991,8 +884,7 @@ class DeerEngine:
             rc = self.lib.deer_step_plan_run(nat["plan"], int(self._si_np[0]), self._seq, ctypes.c_void_p(main_st.cuda_stream),
                                              nat["chain_streams"], nat["head_stream"], nat["ctl_out"], None)
             if rc == 3:
-                raise abi.DeerHipError("no exit verdict from the device within 20 s" + (" (a hand-off of the one-launch head evaluation "
-                                       "timed out)" if self.head_fused_error() else ""))
+                raise abi.DeerHipError("no exit verdict from the device within 20 s")
             abi.check(rc, "deer_step_plan_run")
             self._ext_from_mirror()
             return self.read_result()
@@ -1288,17 +1180,10 @@ class DeerEngine:
             ext = self._hm[W * (1 + self.B):].view(np.float32).reshape(self.B, 2, 64)
             self.act_ext_host.numpy()[:, 1:3] = ext
 
-    def _check_device_errors(self):
-        """the experimental persistent trunk layer reports a timed-out barrier in an error word: a step whose kernels gave up waiting ran
-        on with undefined data, so the step raises instead of returning a result"""
-        if getattr(self, "_persistent_on", False) and self.persistent_layer_error() != 0:
-            raise abi.DeerHipError(f"persistent trunk layer: barrier timed out {self.persistent_layer_error_detail()}")
-
     def read_result(self, src=None):
         """Decode the per-environment control blocks (int32 numpy view; default: the pinned read-back buffer).  multi_step_action = A > 1:
         ``pose`` is (6 A,) = A consecutive 6-DoF actions and ``gripper`` / ``gripper_logit`` are (A,) tensors, the layout of the
         reference head's outputs (action_head.py:472-473, eval_utils.py:468-471)."""
-        self._check_device_errors()
         W = abi.CTL_WORDS
         ci = (self._ctl_host_np if src is None else src).reshape(self.B, W)
         cf = ci.view(np.float32)

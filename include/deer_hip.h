@@ -248,30 +248,6 @@ int deer_xattn_fused_packed(const void* x_hi, const void* x_lo, int d, const voi
                             int n_per_media, int n_kv, const void* Wo_p, float* out, long slab_stride, int T, int heads, float scale,
                             const int* ctl, void* stream);
 
-/* N1 experiment (csrc/persistent_layer.hip): ONE gated x-attn + MPT decoder layer of the one-environment trunk (flamingo_lm.py:46-83) as ONE
- * persistent launch of 256 workgroups - the twelve phases are the device functions of the kernels above, a device-wide barrier at every
- * seam.  Bit-identical to the twelve-launch layer; slower; selected by DEER_PERSISTENT_LAYER=1 only.  All buffers as the
- * spine lays them out: x f32 [T, d] (in / out), slab_a f32 (>= 16 slabs of [16, d]), qkv f32 [T, 3d], stats [3d/32][16][2], xn / h / ao
- * planes (xn in MFMA-fragment order), kv bf16 media K|V of this layer, weights packed (deer_pack_weight_mfma16).  pending_s > 0: the previous
- * layer's mlp_down slabs (in slab_a) are folded in first; hidden_out != NULL: x += this layer's mlp_down slabs and the result is copied out
- * (hidden_states[i]); else they stay pending in slab_a (s_down slabs).  barrier: 192 uint32 (zero before the FIRST launch; cumulative after), error: int32, raised when a
- * barrier times out. */
-typedef struct deer_trunk_layer_args {
-  int T, d, xinner, heads, n_heads, ffw, n_kv, n_per_media, ld_kv, NS, pending_s, qk_ln, s_w2, s_wo, s_down;
-  float eps, xattn_scale, alibi_bias_max;
-  float *x, *slab_a, *qkv, *stats, *prev_hidden, *hidden_out;
-  void *xn_hi, *xn_lo, *h_hi, *h_lo, *ao_hi, *ao_lo;
-  const void* kv;
-  const int* text_time;
-  const unsigned char* key_mask;
-  const float *x_nw, *x_nb, *x_ag, *x_fnw, *x_fnb, *x_fg, *ln1w, *ln1b, *ln2w, *ln2b, *qlnw, *klnw;
-  const void *x_wq, *x_wo, *x_w1, *x_w2, *wqkv, *wo, *wup, *wdown;
-  unsigned* barrier;
-  int* error;
-  int* trace;   /* NULL or 16 rows x 4 int32: row e = {clock lo, clock hi (100 MHz), workgroup} of the LAST arrival at barrier e, row 0 = entry of workgroup 0; [3] = timeouts at e */
-} deer_trunk_layer_args;
-int deer_trunk_layer_persistent(const deer_trunk_layer_args* a, void* stream);
-
 /* deer_resadd_ln for the env-batch vision tower (d == 1024, bf16 LayerNorm output, no control block): rows_per_wg = 2 or 4 rows per workgroup,
  * all loads of all rows in flight before the first use, one pair of block reductions for the R rows.  Per row bit-identical to deer_resadd_ln,
  * which selects it from 2048 rows on (open_clip ResidualAttentionBlock residual + ln_1 / ln_2 of the next op). */
@@ -411,27 +387,6 @@ int deer_head_final_env(const float* src, int src_stride, int in_dim, int pro, c
 /* writes n_envs rows (f32 [n_envs][16], device memory when rows_on_device, else host memory copied into the launch) and n_envs caps (host
  * int32) into an env_exit table, as one launch on `stream`. */
 int deer_env_exit_write(float* env_exit, const float* rows, int rows_on_device, const int* caps, int n_envs, void* stream);
-/* ---- one head evaluation as ONE launch (csrc/head.hip: head_fused_kernel; replaces the eight launches above on control steps of one
- * environment: pool -> L <= 4 LSTM layers (recurrent half from deer_head_lstm_hh) -> <= 3 hidden Linears -> output Linear + exit gate).
- * G workgroups stay resident; the vectors between the phases travel as data-tagged 8-byte granules (relaxed agent-scope atomics), the
- * tag = number of evaluations the exchange buffer has served.  xg: deer_head_fused_granules() * 8 bytes, zeroed once; err: int32[2]
- * zeroed once = {raised when a hand-off timed out, evaluation counter}.  Returns DEER_ERR_SHAPE for what it does not take (no control block, COMMIT kind, f32 weights,
- * more than one environment, d or H > 2048): the caller then uses the separate kernels.  Same arithmetic per row as those kernels. */
-typedef struct deer_head_fused_args {
-  const float* feats; int T, d, avg; const unsigned char* key_mask; const int* cmap;
-  int B, H, L, n_fc, lstm_ln, mlp_ln;
-  int fc_dim[3];
-  const void* w_ih[4]; const float* b_ih[4]; const float* ln_w[4]; const float* ln_b[4];   /* ln_*[l]: LayerNorm of layer l's OUTPUT (lstm_ln) */
-  const float* ghh; const float* c_prev; float* h_tmp; float* c_tmp;
-  const void* fw[3][2]; const float* fb[3][2]; const float* fln_w[3][2]; const float* fln_b[3][2];
-  const void* Wa; const float* ba; const void* Wg; const float* bg;
-  int* ctl; int kind, layer, slot; const float* thresholds; int force, thr_type, leq;
-  float* h_state; float* c_state; float* action_dbg; float eps; int A; float* act_ext;
-  unsigned long long* xg; int* err; int max_in, gather_waves;                               /* max_in, gather_waves: filled by the launcher */
-  unsigned long long* trace;                                                                /* NULL, or 64 x u64: 100 MHz time stamps of workgroup 0 at the phase boundaries (tools/bench_head_eval.py) */
-} deer_head_fused_args;
-long deer_head_fused_granules(int B, int d, int H, int L, int n_fc, const int* fc_dim);
-int deer_head_fused(const deer_head_fused_args* args, int w_is_f32, int n_workgroups, void* stream);
 /* ---- window mode of the head (csrc/head_seq.hip): DeterministicDecoder.forward on N sequences of L steps, action_head.py:499-611 ----
  * Layer-major pieces that deer_head_sequence (deer_model.h) chains; w_kind: 0 bf16, 1 f32, 2 fp16 weight rows (nn.Linear layout [N][K]).
  * deer_head_seq_pool        AdaptiveMax/AvgPool1d over the T rows of each of M (sequence, step) rows (action_head.py:519-520; no key mask

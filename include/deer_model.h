@@ -63,6 +63,8 @@ typedef struct deer_config {
 typedef struct deer_model deer_model;
 
 /* ---- construction (host only) ---------------------------------------------------------------------------------- */
+/* DEER_ERR_SHAPE (and one line on stderr) while DEER_HEAD_FUSED, DEER_PERSISTENT_LAYER or DEER_ONE_GRAPH is set to anything but empty or 0:
+ * the knobs of removed experiments */
 int deer_model_create(const deer_config* cfg, deer_model** out);
 void deer_model_destroy(deer_model* m);
 long deer_model_arena_bytes(const deer_model* m);      /* device bytes for the weights (bf16 GEMM operands, f32 norms/biases) */
@@ -95,12 +97,6 @@ int deer_model_buffer(const deer_model* m, int which, const char* name, long* of
  * (DEER_COMPACT=0 at creation turns it off); changing it affects what is enqueued / captured afterwards.  Results per environment are
  * bit-identical either way. */
 int deer_model_set_compaction(deer_model* m, int on);
-/* one-environment control steps: head evaluation as ONE launch (deer_head_fused; an experiment, off by default: measured slower than the
- * eight separate kernels) or as the eight separate kernels (default) */
-int deer_model_set_head_fused(deer_model* m, int on);
-/* N1 experiment (csrc/persistent_layer.hip): every trunk layer of a one-environment step as ONE persistent launch (12 phases, device-wide
- * barriers) instead of twelve launches.  Bit-identical, slower, and only safe with ONE engine per GPU: off unless DEER_PERSISTENT_LAYER=1. */
-int deer_model_set_persistent_layer(deer_model* m, int on);
 int deer_model_configure_exit(deer_model* m, const int* exit_ids, int n_exit, int max_layer, int thr_type, int leq);
 int deer_model_real_num_exit(const deer_model* m);
 /* Per-environment operating points (one env batch carrying several exit ratios / DeeR-S and DeeR-B caps side by side).  rows: f32
@@ -109,8 +105,7 @@ int deer_model_real_num_exit(const deer_model* m);
  * (the controller's min(max_layer - 1, last exit); a cap beyond the last exit means the last exit): each must then be one of the
  * configured exits, else DEER_ERR_SHAPE (deer_model_configure_exit's rule).  n_envs must be the
  * model's.  The table is written by one launch on `stream` and read by every exit check at replay: captured pieces stay valid as long as
- * the largest cap (the plan's last layer, deer_model_max_layer) does not change.  DEER_ERR_SHAPE while the one-launch head evaluation or the
- * persistent trunk layer is on (both know the shared row only; they refuse to be switched on while a table is active).
+ * the largest cap (the plan's last layer, deer_model_max_layer) does not change.
  * deer_model_clear_env_exit returns to the shared row and the configured cap; deer_model_configure_exit clears the table too. */
 int deer_model_set_env_exit(deer_model* m, const float* rows, const int* caps, int n_envs, void* stream);
 int deer_model_set_env_exit_device(deer_model* m, const float* rows, const int* caps, int n_envs, void* stream);

@@ -112,3 +112,39 @@ def test_spine_parameter_inventory_matches_the_reference_state_dict_names(built)
             assert lib.deer_model_configure_exit(h, ids, 4, 7, 0, 1) != 0      # deepest reachable layer 6 is not an exit
             assert lib.deer_model_configure_exit(h, ids, 4, 8, 0, 1) == 0
         lib.deer_model_destroy(h)
+
+
+@pytest.mark.parametrize("knob", ["DEER_HEAD_FUSED", "DEER_PERSISTENT_LAYER", "DEER_ONE_GRAPH"])
+def test_knob_of_a_retired_experiment_refuses_model_creation(built, knob, monkeypatch, capfd):
+    """The one-launch head evaluation, the persistent trunk layer and the one-graph dynamic step were removed.  Their
+    switches must not turn into knobs that silently do nothing: deer_model_create refuses while one is set to an enabling value (anything
+    but unset, empty or 0) and names it on stderr."""
+    import ctypes
+    from deer_vla_amd.config import deer_tiny
+    from deer_vla_amd.engine import config_to_c
+    lib = abi.lib()
+    cc = config_to_c(deer_tiny(), 1, 32)
+
+    def create():
+        h = ctypes.c_void_p()
+        rc = lib.deer_model_create(ctypes.byref(cc), ctypes.byref(h))
+        if rc == 0:
+            lib.deer_model_destroy(h)
+        else:
+            assert not h.value
+        return rc
+
+    for other in ("DEER_HEAD_FUSED", "DEER_PERSISTENT_LAYER", "DEER_ONE_GRAPH"):
+        monkeypatch.delenv(other, raising=False)
+    assert create() == 0
+    for off in ("", "0"):
+        monkeypatch.setenv(knob, off)
+        assert create() == 0
+    capfd.readouterr()
+    for on in ("1", "true", "2"):
+        monkeypatch.setenv(knob, on)
+        assert create() != 0
+        err = capfd.readouterr().err
+        assert knob in err and "retired experiment, see DESIGN.md" in err and len(err.strip().splitlines()) == 1, err
+    monkeypatch.delenv(knob)
+    assert create() == 0

@@ -6,7 +6,6 @@ Tolerances (BASELINE.json north_star): action outputs within 1e-2 for the bf16 p
 The oracle / golden weights are the bf16-representable weights the engine holds, so the two arms differ only by
 bf16 rounding of activations and summation order."""
 import numpy as np
-import os
 
 import pytest
 import torch
@@ -821,7 +820,7 @@ def test_compaction_of_exited_environments_is_bit_identical_to_the_uncompacted_b
     instruction lengths (padding masks follow the environment, not the slot), 256 trunk rows (two row blocks), graph pieces and eager
     single-stream enqueueing.  ``exits``: CONSECUTIVE exit layers - every layer from 2 on is then a compaction layer and
     the exit check of layer i - 1 is still running on the side stream while layer i gathers: the gather may only drop environments whose
-    verdict the stream has ordered (exit layer <= i - 2, csrc/resadd_body.h), else workgroups could disagree about the packing."""
+    verdict the stream has ordered (exit layer <= i - 2, csrc/norm_embed.hip), else workgroups could disagree about the packing."""
     cfg = deer_tiny()
     sd = syn.make_synthetic_state(cfg, 3, bf16_round=True)
     _compaction_vs_uncompacted(cfg, sd, B, lens, use_graph, exits)
@@ -896,84 +895,3 @@ def test_compaction_in_the_mpt7b_shaped_trunk_is_bit_identical_to_the_uncompacte
     # a gather at layer i drops the environments that exited at layer i - 2 while another one still runs layer i
     gathers = {l + 2 for ex in steps for l in ex if l + 2 <= max(ex)}
     assert any(cfg.has_xattn(i) for i in gathers) and any(not cfg.has_xattn(i) for i in gathers), (gathers, steps)
-
-
-# the full-size variants of the two OFF-BY-DEFAULT experiments (one-launch head evaluation, persistent trunk layer) cost 40 s each:
-# DEER_TEST_EXPERIMENTS=1 runs them (last run: profiles/r05_m_gpu_suite_tail.txt, 1084 passed with both)
-EXPERIMENT_SIZES = ["tiny", "3b"] if os.environ.get("DEER_TEST_EXPERIMENTS") == "1" else ["tiny"]
-
-
-@pytest.mark.parametrize("size", EXPERIMENT_SIZES)
-def test_one_launch_head_evaluation_matches_the_eight_launch_form(size):
-    """on control steps of one environment every head evaluation (pseudo action, exit checks) CAN run as ONE launch
-    (csrc/head.hip: head_fused_kernel - resident workgroups, the vectors between the phases as data-tagged granules; off by default: it
-    measured slower than the eight launches, profiles/r05_e_*).  Every row keeps
-    the arithmetic of the separate kernels (k split over the lanes, in-wave sums, one wave per LayerNorm row, head_final_body), so a
-    dynamic episode with LSTM carry must give the same exit layers and - to the last bit, or within float rounding where hipcc
-    contracts a product differently in the two instantiations - the same actions, deltas and LSTM state; eager and graph pieces; no
-    hand-off may time out."""
-    cfg = deer_tiny() if size == "tiny" else deer_3b(max_layer=12)
-    sd = syn.make_synthetic_state(cfg, 3, bf16_round=True) if size == "tiny" else full_size_state(cfg, 0, std="0.02", bf16_round=True)
-    a = DeerEngine(cfg, sd)
-    b = DeerEngine(cfg, None, weights_from=a)
-    a.set_head_fused(True)                                        # off by default since it measured slower (DESIGN.md 4.1)
-    b.set_head_fused(False)
-    inputs = make_inputs(cfg, 10 if size == "tiny" else 6)
-    thr, _ = probe_thresholds(cfg, sd, inputs, 12, iters=1)
-    worst = 0.0
-    for use_graph in (False, True):
-        for eng in (a, b):
-            eng.configure_exit(cfg.exit_ids(), 12, 1)
-            eng.set_thresholds(thr)
-            eng.reset()
-        seen = set()
-        for s, (rgb, grip, ids, mask) in enumerate(inputs):
-            ra, rb = a.step(rgb, grip, ids, mask, use_graph=use_graph), b.step(rgb, grip, ids, mask, use_graph=use_graph)
-            assert ra["exit_layer"] == rb["exit_layer"] and ra["n_evals"] == rb["n_evals"], (use_graph, s, ra["exit_layer"], rb["exit_layer"])
-            worst = max(worst, float((ra["pose"] - rb["pose"]).abs().max()), abs(ra["gripper"] - rb["gripper"]))
-            da, db = torch.nan_to_num(ra["deltas"], nan=-1.0), torch.nan_to_num(rb["deltas"], nan=-1.0)
-            assert torch.equal(da < 0, db < 0)
-            worst = max(worst, float((da - db).abs().max()))
-            seen.add(ra["exit_layer"])
-        torch.cuda.synchronize()
-        worst = max(worst, float((a.h_state - b.h_state).abs().max()), float((a.c_state - b.c_state).abs().max()))
-        assert len(seen) > 1, seen
-    assert a.head_fused_error() == 0
-    print(f"\n[one-launch head, {size}] worst |fused - separate| over actions / deltas / LSTM state: {worst:.2e}")
-    assert worst < 2e-6, worst
-
-
-@pytest.mark.parametrize("size", EXPERIMENT_SIZES)
-def test_persistent_layer_launch_is_bit_identical_to_the_twelve_launch_layer(size):
-    """N1 experiment (csrc/persistent_layer.hip): every trunk layer of a one-environment step as ONE persistent launch - the same device
-    functions as the twelve kernels, a device-wide barrier at every seam.  Hidden states of every layer, actions and exit layers must be
-    BIT-identical to the default schedule (static full depth and a dynamic episode with LSTM carry), and no barrier may time out."""
-    cfg = deer_tiny() if size == "tiny" else deer_3b(max_layer=12)
-    sd = syn.make_synthetic_state(cfg, 3, bf16_round=True) if size == "tiny" else full_size_state(cfg, 0, std="0.02", bf16_round=True)
-    ref = DeerEngine(cfg, sd)
-    per = DeerEngine(cfg, None, weights_from=ref)
-    per.set_persistent_layer(True)
-    inputs = make_inputs(cfg, 6)
-    last = cfg.n_layers - 1
-    for use_graph in (False, True):
-        for s, (rgb, grip, ids, mask) in enumerate(inputs[:3]):
-            outs = []
-            for eng in (ref, per):
-                eng.reset()
-                r = eng.step(rgb, grip, ids, mask, exit_id=last, use_graph=use_graph)
-                torch.cuda.synchronize()
-                outs.append((r, eng.hidden[:, :ids.shape[1]].clone()))
-            assert torch.equal(outs[0][1], outs[1][1]), (use_graph, s)
-            assert torch.equal(outs[0][0]["pose"], outs[1][0]["pose"]) and outs[0][0]["gripper"] == outs[1][0]["gripper"]
-    thr, _ = probe_thresholds(cfg, sd, inputs, 12, iters=1)
-    for eng in (ref, per):
-        eng.configure_exit(cfg.exit_ids(), 12, 1)
-        eng.set_thresholds(thr)
-        eng.reset()
-    per.set_persistent_layer(True)
-    for s, (rgb, grip, ids, mask) in enumerate(inputs):
-        ra, rb = ref.step(rgb, grip, ids, mask), per.step(rgb, grip, ids, mask)
-        assert ra["exit_layer"] == rb["exit_layer"] and torch.equal(ra["pose"], rb["pose"]) and ra["gripper"] == rb["gripper"], s
-    torch.cuda.synchronize()
-    assert torch.equal(ref.h_state, per.h_state)
-    assert per.persistent_layer_error() == 0

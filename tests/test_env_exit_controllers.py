@@ -212,16 +212,6 @@ def test_refusals():
     e.set_env_exit([[0.02] * 3] * 2, [3, 9])                        # beyond the last exit = the last exit (value_net.py:173)
     assert e.ctl_max_layer == 5
     e.clear_env_exit()
-    # the experiments know the shared row only: refused both ways, never a silent read of row 0
-    e.set_env_exit([[0.02] * 3] * 2, [5, 5])
-    with pytest.raises(abi.DeerHipError):
-        e.set_head_fused(True)
-    assert e.lib.deer_model_set_persistent_layer(e._h, 1) == 1
-    e.clear_env_exit()
-    e.set_head_fused(True)
-    with pytest.raises(abi.DeerHipError):
-        e.set_env_exit([[0.02] * 3] * 2, [5, 5])
-    e.set_head_fused(False)
     # layerwise_exit_eval and one-environment engines keep one operating point
     cfg_lw = deer_tiny(layerwise_exit_eval=True)
     lw = MPTFlamingo(cfg_lw, syn.make_synthetic_state(cfg_lw, 3, bf16_round=True), n_envs=2)

@@ -163,7 +163,7 @@ def poison(rows, cols, fmt):
 
 
 def pack_frag(p, T, fmt, fill):
-    """16-bit [T, K] -> MFMA-fragment order [K/32][16 * (k % 32 / 8) + row][8] (csrc/resadd_body.h:179-182); rows >= T: zeros, `poison` or NaN"""
+    """16-bit [T, K] -> MFMA-fragment order [K/32][16 * (k % 32 / 8) + row][8] (csrc/norm_embed.hip: resadd_ln_body); rows >= T: zeros, `poison` or NaN"""
     K = p.shape[1]
     full = {"zero": lambda: torch.zeros(16, K, dtype=TDT[fmt], device="cuda"), "poison": lambda: poison(16, K, fmt),
             "nan": lambda: nans(16, K, dtype=TDT[fmt])}[fill]()
