@@ -1449,6 +1449,72 @@ bool retired_knob_set() {
   return false;
 }
 
+// ---- window mode of the head: the host-side pieces deer_head_sequence_ex and deer_calibrate_values share (csrc/head_seq.hip) -----------
+// Device scratch of a window-mode entry point: allocated at first use, grown on demand.  Host only: a larger request waits for the
+// stream (the smaller buffer may still be in use), frees and allocates.
+bool grow_scratch(void*& buf, size_t& have, size_t need, hipStream_t st) {
+  if (need <= have) return true;
+  if (buf != nullptr) {
+    if (hipStreamSynchronize(st) != hipSuccess) return false;
+    (void)hipFree(buf);
+    buf = nullptr;
+    have = 0;
+  }
+  if (hipMalloc(&buf, need) != hipSuccess) return false;
+  have = need;
+  return true;
+}
+
+struct ScratchTake {                // carves the scratch into float blocks, each 256-byte aligned
+  char* base;
+  size_t off = 0;
+  float* operator()(long n) {
+    float* p = reinterpret_cast<float*>(base + off);
+    off += ((size_t)n * sizeof(float) + 255) & ~size_t(255);
+    return p;
+  }
+};
+
+// Input of LSTM layer l for `rows` rows, projected: layer 0 reads X [rows][d]; a higher layer reads the previous layer's outputs Y
+// [rows][H], LayerNorm'ed into X with that layer's parameters under lstm_layernorm.  PRE [rows][4H] <- input W_ih^T + b_ih.
+int seq_lstm_input(const deer_model* m, const std::vector<LstmW>& lstm_w, int l, float* X, const float* Y, float* PRE, int rows, void* stream) {
+  const int d = m->d, H = m->H;
+  const float* xin = X;
+  int in_dim = d;
+  if (l > 0) {
+    in_dim = H;
+    if (m->c.lstm_layernorm) DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(lstm_w[l - 1].lnw), m->A<float>(lstm_w[l - 1].lnb), rows, H, kEps, 0, stream));
+    else xin = Y;
+  }
+  DEER_TRY(deer_head_seq_gemm(xin, in_dim, m->A<void>(lstm_w[l].wih), m->wkind, m->A<float>(lstm_w[l].bih), PRE, 4L * H, rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+  return DEER_OK;
+}
+
+// The two MLP heads (action_head.py:86-136) on mr rows x_rows (row pitch ld_x, H wide): hidden Linears with ReLU or LayerNorm through the
+// ping-pong buffers Z[head group], then the output Linears straight into act (row pitch ld_act): [pose 6A, tanh | gripper prob A | logit A]
+int seq_mlp_heads(const deer_model* m, const std::vector<FcW>& fc_w, size_t wa, size_t ba, size_t wg, size_t bg, const float* x_rows, long ld_x,
+                  int mr, float* Z[2][2], float* act, long ld_act, void* stream) {
+  const deer_config& c = m->c;
+  const int A = std::max(1, c.multi_step_action), wk = m->wkind;
+  for (int g = 0; g < 2; ++g) {
+    const float* src = x_rows;
+    long lds = ld_x;
+    int kin = m->H;
+    for (int fi = 0; fi < m->n_fc; ++fi) {
+      const FcW& F = fc_w[fi];
+      const int dim = m->fc_dims[fi];
+      float* z = Z[g][fi & 1];
+      DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(F.w[g]), wk, m->A<float>(F.b[g]), z, dim, mr, dim, kin,
+                                  c.mlp_layernorm ? DEER_SEQ_EPI_NONE : DEER_SEQ_EPI_RELU, stream));
+      if (c.mlp_layernorm) DEER_TRY(deer_head_seq_ln(z, dim, z, dim, m->A<float>(F.lnw[g]), m->A<float>(F.lnb[g]), mr, dim, kEps, 1, stream));
+      src = z; lds = dim; kin = dim;
+    }
+    if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wa), wk, m->A<float>(ba), act, ld_act, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
+    else DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wg), wk, m->A<float>(bg), act + 6 * A, ld_act, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
+  }
+  return DEER_OK;
+}
+
 }  // namespace
 
 // ====================================================================================================================
@@ -1786,19 +1852,9 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
   const long n_x = R * xw, n_u = with_state ? R * 2 * d : 0, n_emb = with_state ? R * d : 0, n_pre = R * 4 * H, n_y = R * H,
              n_c = (long)Nc * H, n_z = R * fc_max;
   const size_t need = (size_t)(n_x + n_u + n_emb + n_pre + n_y + 2 * n_c + 4 * n_z) * sizeof(float) + 16 * 256;
-  if (need > m->seq_bytes) {                            // host only: the first call (or a larger one) allocates
-    if (m->seq_scratch != nullptr) {
-      if (hipStreamSynchronize((hipStream_t)stream) != hipSuccess) return DEER_ERR_LAUNCH;
-      (void)hipFree(m->seq_scratch);
-      m->seq_scratch = nullptr;
-      m->seq_bytes = 0;
-    }
-    if (hipMalloc(&m->seq_scratch, need) != hipSuccess) return DEER_ERR_LAUNCH;
-    m->seq_bytes = need;
-  }
-  char* base = reinterpret_cast<char*>(m->seq_scratch);
-  size_t off = 0;
-  auto take = [&](long n) { float* p = reinterpret_cast<float*>(base + off); off += ((size_t)n * sizeof(float) + 255) & ~size_t(255); return p; };
+  hipStream_t st = (hipStream_t)stream;
+  if (!grow_scratch(m->seq_scratch, m->seq_bytes, need, st)) return DEER_ERR_LAUNCH;
+  ScratchTake take{reinterpret_cast<char*>(m->seq_scratch)};
   float* X = take(n_x);
   float* U = with_state ? take(n_u) : nullptr;
   float* EMB = with_state ? take(n_emb) : nullptr;
@@ -1807,7 +1863,6 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
   float* CS = take(n_c);
   float* HZ = take(n_c);
   float* Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
-  hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(HZ, 0, (size_t)n_c * sizeof(float), st) != hipSuccess) return DEER_ERR_LAUNCH;
   const int out_rows_per = last ? 1 : L;
   for (int n0 = 0; n0 < N; n0 += Nc) {
@@ -1826,14 +1881,7 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
     // ---- the LSTM, layer by layer ----
     for (int l = 0; l < Lh; ++l) {
       const LstmW& Lw = lstm_w[l];
-      const float* xin = X;
-      int in_dim = d;
-      if (l > 0) {
-        in_dim = H;
-        if (c.lstm_layernorm) DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(lstm_w[l - 1].lnw), m->A<float>(lstm_w[l - 1].lnb), (int)rows, H, kEps, 0, stream));
-        else xin = Y;
-      }
-      DEER_TRY(deer_head_seq_gemm(xin, in_dim, m->A<void>(Lw.wih), wk, m->A<float>(Lw.bih), PRE, 4L * H, (int)rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+      DEER_TRY(seq_lstm_input(m, lstm_w, l, X, Y, PRE, (int)rows, stream));
       const long so = (long)l * N * H + (long)n0 * H;             // (L_lstm, N, H) state tensors
       if (c0 != nullptr) {
         if (hipMemcpyAsync(CS, c0 + so, (size_t)nc * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return DEER_ERR_LAUNCH;
@@ -1862,23 +1910,7 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
                          hipMemcpyDeviceToDevice, st) != hipSuccess)
       return DEER_ERR_LAUNCH;
     // ---- the two MLP heads (action_head.py:86-136), outputs [pose 6A | gripper prob A | logit A] per row ----
-    float* act = actions + (long)n0 * out_rows_per * 8 * A;
-    for (int g = 0; g < 2; ++g) {
-      const float* src = x_rows;
-      long lds = ld_x;
-      int kin = H;
-      for (int fi = 0; fi < m->n_fc; ++fi) {
-        const FcW& F = fc_w[fi];
-        const int dim = m->fc_dims[fi];
-        float* z = Z[g][fi & 1];
-        DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(F.w[g]), wk, m->A<float>(F.b[g]), z, dim, mr, dim, kin,
-                                    c.mlp_layernorm ? DEER_SEQ_EPI_NONE : DEER_SEQ_EPI_RELU, stream));
-        if (c.mlp_layernorm) DEER_TRY(deer_head_seq_ln(z, dim, z, dim, m->A<float>(F.lnw[g]), m->A<float>(F.lnb[g]), mr, dim, kEps, 1, stream));
-        src = z; lds = dim; kin = dim;
-      }
-      if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wa), wk, m->A<float>(ba), act, 8L * A, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
-      else DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wg), wk, m->A<float>(bg), act + 6 * A, 8L * A, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
-    }
+    DEER_TRY(seq_mlp_heads(m, fc_w, wa, ba, wg, bg, x_rows, ld_x, mr, Z, actions + (long)n0 * out_rows_per * 8 * A, 8L * A, stream));
   }
   return DEER_OK;
 }
@@ -1942,19 +1974,8 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
   const long n_x = R * xw, n_pre = R * 4 * H, n_y = R * H, n_c = Rh * H, n_z = Rc * fc_max, n_act = Rc * 8 * A;
   const size_t need = (size_t)(n_x + n_pre + n_y + n_c + H + 4 * n_z + n_act + Rc) * sizeof(float) + 16 * 256;
   hipStream_t st = (hipStream_t)stream;
-  if (need > m->calib_bytes) {                          // host only: the first call (or a larger one) allocates
-    if (m->calib_scratch != nullptr) {
-      if (hipStreamSynchronize(st) != hipSuccess) return DEER_ERR_LAUNCH;
-      (void)hipFree(m->calib_scratch);
-      m->calib_scratch = nullptr;
-      m->calib_bytes = 0;
-    }
-    if (hipMalloc(&m->calib_scratch, need) != hipSuccess) return DEER_ERR_LAUNCH;
-    m->calib_bytes = need;
-  }
-  char* base = reinterpret_cast<char*>(m->calib_scratch);
-  size_t off = 0;
-  auto take = [&](long n) { float* p = reinterpret_cast<float*>(base + off); off += ((size_t)n * sizeof(float) + 255) & ~size_t(255); return p; };
+  if (!grow_scratch(m->calib_scratch, m->calib_bytes, need, st)) return DEER_ERR_LAUNCH;
+  ScratchTake take{reinterpret_cast<char*>(m->calib_scratch)};
   float* X = take(n_x);
   float* PRE = take(n_pre);
   float* Y = take(n_y);
@@ -1971,15 +1992,7 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
     DEER_TRY(deer_calib_gather(P + (long)b0 * W * NL * d, rand_layers + (long)b0 * W, slot_of, c.n_layers, X, IDX, nb, W, NL, d, stream));
     for (int l = 0; l < Lh; ++l) {
       const LstmW& Lw = m->lstm[l];
-      const float* xin = X;
-      int in_dim = d;
-      if (l > 0) {
-        in_dim = H;
-        if (c.lstm_layernorm) DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(m->lstm[l - 1].lnw), m->A<float>(m->lstm[l - 1].lnb), (int)rows, H, kEps, 0, stream));
-        else xin = Y;
-      }
-      // W_ih of this layer once for history and candidate rows
-      DEER_TRY(deer_head_seq_gemm(xin, in_dim, m->A<void>(Lw.wih), wk, m->A<float>(Lw.bih), PRE, 4L * H, (int)rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+      DEER_TRY(seq_lstm_input(m, m->lstm, l, X, Y, PRE, (int)rows, stream));      // W_ih of this layer once for history and candidate rows
       // history: step t of every window from its step t - 1, (h, c) of every step kept in Y / CS rows (b, t)
       for (int t = 0; t < L; ++t)
         DEER_TRY(deer_calib_lstm_step(PRE + (long)t * 4 * H, (long)L * 4 * H, t > 0 ? Y + (long)(t - 1) * H : nullptr, (long)L * H,
@@ -1995,23 +2008,7 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
       DEER_TRY(deer_head_seq_ln(Y + rh * H, H, X, H, m->A<float>(m->lstm.back().lnw), m->A<float>(m->lstm.back().lnb), (int)rc, H, kEps, 0, stream));
       xo = X;
     }
-    const int mr = (int)rc;
-    for (int g = 0; g < 2; ++g) {
-      const float* src = xo;
-      long lds = H;
-      int kin = H;
-      for (int fi = 0; fi < m->n_fc; ++fi) {
-        const FcW& F = m->fc[fi];
-        const int dim = m->fc_dims[fi];
-        float* z = Z[g][fi & 1];
-        DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(F.w[g]), wk, m->A<float>(F.b[g]), z, dim, mr, dim, kin,
-                                    c.mlp_layernorm ? DEER_SEQ_EPI_NONE : DEER_SEQ_EPI_RELU, stream));
-        if (c.mlp_layernorm) DEER_TRY(deer_head_seq_ln(z, dim, z, dim, m->A<float>(F.lnw[g]), m->A<float>(F.lnb[g]), mr, dim, kEps, 1, stream));
-        src = z; lds = dim; kin = dim;
-      }
-      if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(m->wa), wk, m->A<float>(m->ba), ACT, 8L * A, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
-      else DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(m->wg), wk, m->A<float>(m->bg), ACT + 6 * A, 8L * A, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
-    }
+    DEER_TRY(seq_mlp_heads(m, m->fc, m->wa, m->ba, m->wg, m->bg, xo, H, (int)rc, Z, ACT, 8L * A, stream));
     // ---- deltas of consecutive candidate layers over the 6 A pose values, window-major columns b0 S .. ----
     DEER_TRY(deer_calib_delta(ACT, 8L * A, NL, nb * S, 6 * A, threshold_type, values + (long)b0 * S, n_val, stream));
     if (actions != nullptr &&

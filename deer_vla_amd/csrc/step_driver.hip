@@ -8,9 +8,9 @@
 //   * per pseudo / exit-check layer one head-evaluation graph on the head stream, forked off after that layer.
 // The exit decision is taken on the device; the last kernel of every exit check publishes (sequence number, checks done,
 // verdict) into pinned host memory (csrc/head.hip::check_done).  This driver submits the pieces, keeps at most `lookahead`
-// trunk layers in flight beyond an undecided check, polls the mirror and stops submitting at the exit - the loop that
-// engine.py::_step_segmented runs in Python, as one GIL-free native call (the Python loop spent ~40 us per step before the
-// first graph was submitted and ~25 us per piece; submission here is one hipGraphLaunch per piece).
+// trunk layers in flight beyond an undecided check, polls the mirror and stops submitting at the exit.  It is the only
+// submission loop of the dynamic step (engine.py::_step_segmented calls it): one GIL-free native call, one hipGraphLaunch per
+// piece (the Python loop it replaced spent ~40 us per step before the first graph was submitted and ~25 us per piece).
 #include "common.h"
 #include "../../include/deer_hip.h"
 #include "../../include/deer_model.h"
@@ -84,10 +84,11 @@ extern "C" void deer_step_plan_destroy(deer_step_plan* p) {
 
 // One dynamic control step.  hold: 1 iff cur_step % steps_per_stage != 0 (value_net.py:285-286); seq: the step's sequence number
 // (1 .. 2^24-1, increasing; the caller clears the mirror when it wraps).  chain_streams: streams of chains 1 .. n_chains-1.
-// ctl_out: host int32 [n_envs * 64] <- the environments' control blocks as published with their verdicts.  pieces_out (NULL ok):
-// number of trunk pieces submitted.  Returns DEER_OK, DEER_ERR_LAUNCH, or 3 when no verdict arrived within 20 s.
+// ctl_out: host int32 [n_envs * 64] <- the environments' control blocks as published with their verdicts.  trunk_start_event
+// (NULL ok): a hipEvent_t recorded on the caller's stream after the vision chains have joined and before trunk piece 0 (stage
+// timing).  Returns DEER_OK, DEER_ERR_LAUNCH, or 3 when no verdict arrived within 20 s.
 extern "C" int deer_step_plan_run(deer_step_plan* p, int hold, int seq, void* main_stream, void* const* chain_streams, void* head_stream,
-                                  int* ctl_out, int* pieces_out) {
+                                  int* ctl_out, void* trunk_start_event) {
   if (p == nullptr || seq <= 0 || ctl_out == nullptr || (p->n_chains > 1 && chain_streams == nullptr)) return DEER_ERR_SHAPE;
   hipStream_t ms = reinterpret_cast<hipStream_t>(main_stream);
   hipStream_t hs = head_stream != nullptr ? reinterpret_cast<hipStream_t>(head_stream) : ms;
@@ -114,6 +115,7 @@ extern "C" int deer_step_plan_run(deer_step_plan* p, int hold, int seq, void* ma
       SD_HIP(hipEventRecord(p->ev_join[c], cs(c)));
       SD_HIP(hipStreamWaitEvent(ms, p->ev_join[c], 0));
     }
+  if (trunk_start_event != nullptr) SD_HIP(hipEventRecord(reinterpret_cast<hipEvent_t>(trunk_start_event), ms));
 
   // ---- trunk pieces with head evaluations forked off; stop at the exit ----
   const int* mirror = p->mirror;
@@ -137,7 +139,7 @@ extern "C" int deer_step_plan_run(deer_step_plan* p, int hold, int seq, void* ma
     return load_acquire(mirror + HOSTM_DONE) == seq ? 1 : 0;
   };
   const int n_exits = (int)p->exits.size();
-  int decided = 0, done = 0, launched = 0;
+  int decided = 0, done = 0;
   for (int i = 0; i < p->n_pieces && !done; ++i) {
     while (decided < n_exits && p->exits[decided] + p->lookahead < i) {
       done = poll(decided + 1);
@@ -151,7 +153,6 @@ extern "C" int deer_step_plan_run(deer_step_plan* p, int hold, int seq, void* ma
     // hold for every look-ahead
     if (p->n_envs > 1 && hs != ms && i >= 2 && p->ev_head_done[i - 2] != nullptr) SD_HIP(hipStreamWaitEvent(ms, p->ev_head_done[i - 2], 0));
     SD_HIP(hipGraphLaunch(p->main_g[i], ms));
-    ++launched;
     if (p->head_g[i] != nullptr) {
       if (hs != ms) {
         SD_HIP(hipEventRecord(p->ev_head[i], ms));
@@ -165,7 +166,6 @@ extern "C" int deer_step_plan_run(deer_step_plan* p, int hold, int seq, void* ma
     done = poll(n_exits);
     if (done < 0) return 3;
   }
-  if (pieces_out != nullptr) *pieces_out = launched;
   if (!done) return DEER_ERR_LAUNCH;                                  // the forced exit at the last check always fires
   std::memcpy(ctl_out, const_cast<const int*>(mirror) + CTL_WORDS, sizeof(int) * CTL_WORDS * p->n_envs);
   return DEER_OK;

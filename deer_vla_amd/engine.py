@@ -18,7 +18,6 @@ from __future__ import annotations
 import ctypes
 import gc
 import os
-import time
 from contextlib import contextmanager
 from types import SimpleNamespace
 from typing import Dict, List, Optional, Sequence
@@ -129,6 +128,9 @@ class DeerEngine:
         """n_envs: independent environments evaluated per control step (one "env batch" per rank).  They share every
         weight read: the ViT sees M = 514*n_envs rows, the LLM n_envs*T rows, each environment keeps its own LSTM state,
         thresholds are shared and every environment exits at its own layer (device side)."""
+        if os.environ.get("DEER_NATIVE_STEP", "") not in ("", "1"):
+            raise abi.DeerHipError("DEER_NATIVE_STEP is a retired knob: the native step driver (csrc/step_driver.hip) is the only "
+                                   "submission loop of the dynamic step")
         if not torch.cuda.is_available():
             raise abi.DeerHipError("DeerEngine needs a HIP device (no CPU fallback exists in deer_vla_amd)")
         self.lib = abi.lib()
@@ -178,13 +180,11 @@ class DeerEngine:
         self._side_stream = torch.cuda.Stream(device=self.dev)
         self._drain_events: Dict[torch.cuda.Stream, torch.cuda.Event] = {}
         self._plans = []                                                   # native step plans (own HIP events): freed with the graphs
-        self._native_step = os.environ.get("DEER_NATIVE_STEP", "1") == "1"   # 0: the Python submission / polling loop (debugging)
         self._extra_streams: List[torch.cuda.Stream] = []
         self._use_side = os.environ.get("DEER_SIDE", "1") == "1"          # debugging knobs (README)
         self._lookahead = int(os.environ.get("DEER_LOOKAHEAD", self.LOOKAHEAD))
         self._seq = 0
         self._ids_tag = None
-        self._trace = None                            # debugging aid: list of (label, event, host time) per piece
         self._time_stages = False                     # per-stage GPU times of pipelined steps -> last_stage_ms (eval_time hook)
         self.last_stage_ms: Dict[str, float] = {}
         # controller configuration (set by configure_exit)
@@ -280,7 +280,7 @@ class DeerEngine:
         # host mirror of the verdicts (pinned => device-visible and system-coherent): see csrc/head.hip::check_done
         # (multi_step_action > 1: + [B][128] f32 behind the control blocks - the committed and the ensemble action of every environment)
         self.host_mirror = torch.zeros((1 + B) * abi.CTL_WORDS + (B * 128 if self.A > 1 else 0), dtype=torch.int32).pin_memory()
-        self._hm = self.host_mirror.numpy()                                 # polled by the host between graph segments
+        self._hm = self.host_mirror.numpy()                                 # polled by the native step driver (csrc/step_driver.hip)
         self.step_info_pinned = torch.zeros(4, dtype=torch.int32).pin_memory()   # read by the device in pipelined steps
         self._si_np = self.step_info_pinned.numpy()
         mptr = self.host_mirror.data_ptr()
@@ -760,9 +760,6 @@ class DeerEngine:
                     with torch.cuda.stream(cst[c]):
                         C[part][c].replay()
         if nch > 1:
-            if self._trace is not None:
-                self._trace.append(("chain0 (main)", self._mark(main_st), time.perf_counter()))
-                self._trace.append(("chain1 (side)", self._mark(cst[1]), time.perf_counter()))
             for c in range(1, nch):
                 if cst[c] is not main_st:
                     ev = C["ev_join"][c]
@@ -854,7 +851,7 @@ class DeerEngine:
             self.hold_dev.copy_(self.step_info_pinned, non_blocking=True)
             self._enqueue_step(T, use_mask, None)                 # eager warm-up of the whole step - a real step
             main_st.synchronize()
-            P = {"main": [], "head": {}, "ev": {}, "ev_done": {}}
+            P = {"main": [], "head": {}}
             self._vision_chain_graphs()
             for i, need_pseudo, is_exit, _ in plan:
                 g = torch.cuda.CUDAGraph()
@@ -868,8 +865,6 @@ class DeerEngine:
                     with _capture(gh):
                         self.enqueue_dynamic_heads(T, i, use_mask=use_mask)
                     P["head"][i] = gh
-                    P["ev"][i] = torch.cuda.Event()
-                    P["ev_done"][i] = torch.cuda.Event()
             P["native"] = self._make_step_plan(P, plan)
             self._graphs[key] = P
             self.ctl_host.copy_(self.ctl, non_blocking=True)     # first call: verdict through the ordinary read-back
@@ -878,81 +873,24 @@ class DeerEngine:
             main_st.synchronize()
             return self.read_result()
 
-        if self._native_step and self._trace is None and not self._time_stages:
-            # the native driver (csrc/step_driver.hip): the same submission / look-ahead / polling loop as below, one GIL-free call
-            nat = P["native"]
-            rc = self.lib.deer_step_plan_run(nat["plan"], int(self._si_np[0]), self._seq, ctypes.c_void_p(main_st.cuda_stream),
-                                             nat["chain_streams"], nat["head_stream"], nat["ctl_out"], None)
-            if rc == 3:
-                raise abi.DeerHipError("no exit verdict from the device within 20 s")
-            abi.check(rc, "deer_step_plan_run")
-            self._ext_from_mirror()
-            return self.read_result()
-
-        hm, seq, W = self._hm, self._seq, abi.CTL_WORDS
-        if self._trace is not None:
-            self._trace.append(("start", self._mark(main_st), time.perf_counter()))
-        side = self._side_stream if self._use_side else main_st
-        LOOK = self._lookahead
-        exits = [i for i, _, is_exit, _ in plan if is_exit]      # exit k is decided by the check at layer exits[k]
-        decided = 0                                              # number of exit checks whose verdict the host has seen
-        done = False
-
-        def poll(n_checks):
-            """spin until `n_checks` checks of this step are decided or every environment exited"""
-            want, spins, t_dead = seq * 64 + n_checks, 0, None
-            while hm[abi.HOSTM_DONE] != seq and hm[abi.HOSTM_PROGRESS] < want:
-                spins += 1
-                if spins & 0xFFFF == 0:
-                    t_dead = t_dead or time.monotonic() + 20.0
-                    if time.monotonic() > t_dead:
-                        raise abi.DeerHipError("no exit verdict from the device within 20 s (check %d)" % (n_checks - 1))
-            return hm[abi.HOSTM_DONE] == seq
-
+        # the native driver (csrc/step_driver.hip): submission, look-ahead and polling of the verdict mirror in one GIL-free call
+        nat = P["native"]
         tm = self._time_stages
-        if tm:
+        if tm:                                                   # per-stage GPU time of this step (reference hooks: eval_time)
             ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
             ev[0].record(main_st)
-        self._replay_vision_chains(main_st, side)
+            ev[1].record(main_st)                                # creates the handle; the driver records it again after the vision chains joined
+        rc = self.lib.deer_step_plan_run(nat["plan"], int(self._si_np[0]), self._seq, ctypes.c_void_p(main_st.cuda_stream),
+                                         nat["chain_streams"], nat["head_stream"], nat["ctl_out"],
+                                         ctypes.c_void_p(ev[1].cuda_event) if tm else None)
+        if rc == 3:
+            raise abi.DeerHipError("no exit verdict from the device within 20 s")
+        abi.check(rc, "deer_step_plan_run")
         if tm:
-            ev[1].record(main_st)
-        for i, need_pseudo, is_exit, _ in plan:
-            # keep at most LOOKAHEAD trunk layers in flight beyond an undecided check
-            while decided < len(exits) and exits[decided] + LOOK < i:
-                done = poll(decided + 1)
-                decided += 1
-                if done:
-                    break
-            if done:
-                break
-            if self.B > 1 and side is not main_st and i >= 2 and (i - 2) in P["ev_done"]:
-                main_st.wait_event(P["ev_done"][i - 2])           # compaction layer: the verdict of check i - 2 is complete (see csrc/step_driver.hip)
-            P["main"][i].replay()
-            if self._trace is not None:
-                self._trace.append(("main%d" % i, self._mark(main_st), time.perf_counter()))
-            if need_pseudo or is_exit:
-                if side is main_st:
-                    P["head"][i].replay()
-                else:
-                    hev = P["ev"][i]
-                    hev.record(main_st)
-                    side.wait_event(hev)
-                    with torch.cuda.stream(side):
-                        P["head"][i].replay()
-                    if self.B > 1:
-                        P["ev_done"][i].record(side)
-                if self._trace is not None:
-                    self._trace.append(("head%d" % i, self._mark(side), time.perf_counter()))
-        if not done:
-            done = poll(len(exits))
-        if not done:                                             # the forced exit at the last check always fires
-            raise abi.DeerHipError("dynamic step finished without an exit verdict")
-        if tm:                                                   # per-stage GPU time of this step (reference hooks: eval_time)
-            main_st.wait_stream(side)
+            main_st.wait_stream(self._side_stream if self._use_side else main_st)
             ev[2].record(main_st)
             ev[2].synchronize()
             self.last_stage_ms = {"vision": ev[0].elapsed_time(ev[1]), "llm_and_exit_checks": ev[1].elapsed_time(ev[2])}
-        self._ctl_host_np[:] = hm[W:W * (1 + self.B)]            # keep the ordinary read-back buffer current (ctl_host users)
         self._ext_from_mirror()
         return self.read_result()
 
@@ -1165,12 +1103,6 @@ class DeerEngine:
         else:
             raise NotImplementedError(threshold_type)
         return v.flatten(1, 2)                                                 # (n_exit, bs * W/2), window-major like value_net.py:160
-
-    @staticmethod
-    def _mark(stream):
-        e = torch.cuda.Event(enable_timing=True)
-        e.record(stream)
-        return e
 
     def _ext_from_mirror(self):
         """multi_step_action > 1, pipelined steps: the committed / ensemble actions travel with the verdict behind the control blocks of

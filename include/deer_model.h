@@ -209,9 +209,10 @@ typedef struct deer_step_plan deer_step_plan;
 int deer_step_plan_create(int n_chains, void* const* chain_head, void* const* chain_tail, int n_pieces, void* const* main_graphs,
                           void* const* head_graphs, const int* is_exit, int lookahead, int n_envs, int* step_info_pinned,
                           int* host_mirror, deer_step_plan** out);
-/* returns 0, 2 (HIP error) or 3 (no verdict within 20 s); ctl_out: host int32[n_envs * 64]; pieces_out: NULL or trunk pieces submitted */
+/* returns 0, 2 (HIP error) or 3 (no verdict within 20 s); ctl_out: host int32[n_envs * 64]; trunk_start_event: NULL or a
+ * hipEvent_t recorded on main_stream after the vision chains have joined, before trunk piece 0 */
 int deer_step_plan_run(deer_step_plan* p, int hold, int seq, void* main_stream, void* const* chain_streams, void* head_stream,
-                       int* ctl_out, int* pieces_out);
+                       int* ctl_out, void* trunk_start_event);
 void deer_step_plan_destroy(deer_step_plan* p);
 
 /* ---- in-situ profiler: HIP events around every kernel-launching call of the spine (bench.py roofline pass) --------- */

@@ -151,6 +151,40 @@ def test_eval_time_hook_reports_per_stage_gpu_times():
     assert 0.0 < model.llm_inference_time < model.forward_time and 0.0 < model.vision_time < model.forward_time
 
 
+def test_eval_time_hook_on_a_dynamic_step_times_the_stages_and_leaves_the_results_unchanged():
+    """``eval_time=True`` on a DYNAMIC step (native ExitController, exit decided on the device): the pipelined step reports the GPU
+    time of the vision tower and of the trunk + exit checks like the static step does, and timing a step changes nothing of what
+    it computes - exit layer and action bit-equal to a freshly built second model fed the same steps with ``eval_time=False``.
+    Thresholds [0, 1e5, 1e5] with the "<=" criterion: the first check (an L2 distance <= 0) does not fire, the second always
+    does, so every step ends at the inner exit layer 3 of deer_tiny's exits [1, 3, 5], not at the forced last one."""
+    from deer_vla_amd.config import deer_tiny
+    from deer_vla_amd.flamingo_mpt import MPTFlamingo
+    cfg = deer_tiny()
+    assert cfg.exit_ids() == [1, 3, 5]
+    sd = syn.make_synthetic_state(cfg, 3, bf16_round=True)
+    steps = [syn.synthetic_step_inputs(cfg, s) for s in range(4)]         # the first call captures the graph pieces
+
+    def run(eval_time):
+        model = MPTFlamingo(cfg, sd)
+        vn = ActionValueNet(model.get_all_exit_idx(), model.extra_exit, cfg.exit_interval, cfg.window_size, "L2")
+        ctl = ExitController(vn, model.get_all_exit_idx(), steps_per_stage=1, leq=True, exit_dist="exp", max_layer=12)
+        ctl._set_threshold_value([0.0, 1e5, 1e5])
+        outs = []
+        for s, (rgb, grip, ids, mask) in enumerate(steps):
+            ctl.module.set_timestep(s)
+            o = model(vision_x=rgb.cuda(), lang_x=ids.cuda(), attention_mask=mask.cuda(), vision_gripper=grip.cuda(), exit_id=None,
+                      dynamic_early_exit=True, exit_controller=ctl, eval_time=eval_time)
+            outs.append((o.exit_layer, o.logits[0].cpu().clone(), o.logits[1].cpu().clone()))
+        return model, outs
+
+    timed, a = run(True)
+    assert 0.0 < timed.llm_inference_time < timed.forward_time and 0.0 < timed.vision_time < timed.forward_time
+    _, b = run(False)
+    for s in range(4):
+        assert a[s][0] == b[s][0] == 3, s
+        assert torch.equal(a[s][1], b[s][1]) and torch.equal(a[s][2], b[s][2]), s
+
+
 @pytest.mark.parametrize("name,precision", [("deer_forward_state.npz", "fp16"), ("deer_forward_sep.npz", "fp16"), ("deer_forward_sep.npz", "bf16"),
                                             ("deer_forward_state.npz", "fp32"), ("deer_forward_sep.npz", "fp32")])
 def test_use_state_and_sep_resampler_variants_match_reference_forward(name, precision):

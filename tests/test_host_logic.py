@@ -294,3 +294,23 @@ def test_native_controller_is_callable_with_the_reference_protocol(name):
             ep, eg = net.get_ensemble_action()                   # value_net.py:92-95 on the host-side action list
             acts = net.action_list[-2:]
             assert torch.equal(ep, torch.stack([x[0] for x in acts]).mean(0)) and torch.equal(eg, torch.stack([x[1] for x in acts]).mean(0))
+
+
+def test_retired_native_step_knob_refuses_engine_construction(monkeypatch):
+    """DEER_NATIVE_STEP=0 used to select a Python copy of the step driver's submission loop.  The copy is gone; the knob must not
+    silently do nothing: DeerEngine refuses it as its first statement, before any device is touched (so it is seen here, without
+    a GPU).  Unset, empty or 1 (the old default) pass that line."""
+    import pytest
+    from deer_vla_amd._abi import DeerHipError
+    from deer_vla_amd.engine import DeerEngine
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: False)        # past the refusal, construction stops at the device check
+    for off in ("0", "2", "no"):
+        monkeypatch.setenv("DEER_NATIVE_STEP", off)
+        with pytest.raises(DeerHipError, match="DEER_NATIVE_STEP is a retired knob"):
+            DeerEngine(deer_tiny(), None)
+    monkeypatch.delenv("DEER_NATIVE_STEP")
+    for ok in (None, "", "1"):
+        if ok is not None:
+            monkeypatch.setenv("DEER_NATIVE_STEP", ok)
+        with pytest.raises(DeerHipError, match="needs a HIP device"):
+            DeerEngine(deer_tiny(), None)
