@@ -158,6 +158,12 @@ SIGNATURES = {
     "deer_calib_delta": [P, L, I, I, I, I, P, L, P],
     "deer_pool_exit_layers": [P, I, I, P, P],
     "deer_calibrate_values": [P, P, P, I, I, I, P, P, P],
+    # per-exit demonstration loss (csrc/exit_eval.hip, include/deer_model.h deer_exit_outputs)
+    "deer_window_gather_layers": [P, P, P, I, P, I, I, I, I, I, P],
+    "deer_exit_losses": [P, P, P, I, L, I, F, P, P, P, P],
+    "deer_pool_window_layers": [P, I, I, P, P],
+    "deer_exit_outputs": [P, P, I, P, P, I, I, P, P],
+    "deer_exit_n_heads": [P],
     "deer_model_scratch_bytes": [P],
     "deer_model_n_chains": [P],
     "deer_prof_enable": [P, I],

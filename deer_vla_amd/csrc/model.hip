@@ -211,6 +211,8 @@ struct deer_model {
   size_t seq_bytes = 0;
   void* calib_scratch = nullptr;    // deer_calibrate_values: device scratch of the calibration pass, same rule
   size_t calib_bytes = 0;
+  void* exit_scratch = nullptr;     // deer_exit_outputs: pooled / gathered feature rows of the all-exits pass, same rule
+  size_t exit_bytes = 0;
   bool head_pre = true;             // recurrent half of the LSTM head once per control step (DEER_HEAD_PRE=0: every evaluation streams W_hh again)
   bool ghh_valid = false;           // the pre-pass result matches h_state: set by deer_begin_step, cleared by deer_model_head_state_changed
   bool compact = true;              // env batches: compaction of exited environments (DEER_COMPACT=0 / deer_model_set_compaction)
@@ -1585,6 +1587,7 @@ void deer_model_destroy(deer_model* m) {
   for (hipEvent_t e : m->ev_pool) (void)hipEventDestroy(e);
   if (m->seq_scratch != nullptr) (void)hipFree(m->seq_scratch);
   if (m->calib_scratch != nullptr) (void)hipFree(m->calib_scratch);
+  if (m->exit_scratch != nullptr) (void)hipFree(m->exit_scratch);
   delete m;
 }
 
@@ -2019,7 +2022,84 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
   return DEER_OK;
 }
 
-long deer_model_scratch_bytes(const deer_model* m) { return (long)(m->seq_bytes + m->calib_bytes); }
+// ---- the all-exits window forward (flamingo_mpt.py:463-517) on pooled features (csrc/exit_eval.hip) ----------------------------------
+// the layers that carry a head, the last layer and the layers the sampling strategies draw from are one list: get_all_exit_idx
+// (flamingo_mpt.py:268-270) = every exit_interval-th layer below the last one + the last one.  -1: more than the pooling kernel takes.
+static int window_exit_layers(const deer_model* m, int* lay) {
+  const deer_config& c = m->c;
+  int n = 0;
+  for (int i = c.exit_interval - 1; i < c.n_layers - 1; i += c.exit_interval) {
+    if (n + 1 >= DEER_CALIB_MAX_NL) return -1;
+    lay[n++] = i;
+  }
+  lay[n++] = c.n_layers - 1;
+  return c.n_layers > DEER_CALIB_MAX_LAYERS ? -1 : n;
+}
+
+int deer_pool_window_layers(deer_model* m, int n_frames, int T, float* P, void* stream) {
+  const deer_config& c = m->c;
+  if (m->ws == nullptr || P == nullptr || n_frames <= 0 || n_frames > m->B || T <= 0 || T > c.max_text_len) return DEER_ERR_SHAPE;
+  const long rows_cap = std::min(m->B * c.max_text_len, kMaxRows);
+  if ((long)n_frames * T > rows_cap) return DEER_ERR_SHAPE;
+  int lay[DEER_CALIB_MAX_NL];
+  const int NE = window_exit_layers(m, lay);
+  if (NE < 0) return DEER_ERR_SHAPE;
+  Bracket b(m, "deer_pool_window_layers", 0, (double)NE * n_frames * (T + 1) * m->d * 4, stream);
+  return deer_calib_pool_layers(m->Wk<float>(m->hidden), rows_cap * m->d, lay, NE, P, n_frames, T, m->d, c.pooling_avg, stream);
+}
+
+int deer_exit_outputs(deer_model* m, const float* P, int T, const int* sel, const float* state, int bs, int W, float* actions, void* stream) {
+  const deer_config& c = m->c;
+  if (m->arena == nullptr || sel == nullptr || actions == nullptr || bs <= 0 || W <= 0 || (bool)c.use_state != (state != nullptr) ||
+      (c.use_state && !m->lw.empty()))
+    return DEER_ERR_SHAPE;
+  int lay[DEER_CALIB_MAX_NL], slot_of[DEER_CALIB_MAX_LAYERS];
+  const int NE = window_exit_layers(m, lay);
+  if (NE < 0) return DEER_ERR_SHAPE;
+  for (int l = 0; l < c.n_layers; ++l) slot_of[l] = -1;
+  for (int k = 0; k < NE; ++k) slot_of[lay[k]] = k;
+  const int d = m->d, A = std::max(1, c.multi_step_action);
+  const long R = (long)bs * W;
+  if (R > 0x7fffffffL / (8 * A * (NE + 2)) || R > 0x7fffffffL / ((long)NE * d)) return DEER_ERR_SHAPE;
+  if (P == nullptr && (m->ws == nullptr || R > m->B)) return DEER_ERR_SHAPE;      // the frames of ONE static pass are the rows of the workspace
+  // scratch (floats): pooled features [R][NE][d] when they come from the workspace, the two gathered selections [2][R][d], one head's rows [R][d]
+  const long n_p = P == nullptr ? R * NE * d : 0, n_x = R * d;
+  const size_t need = (size_t)(n_p + 3 * n_x) * sizeof(float) + 8 * 256;
+  hipStream_t st = (hipStream_t)stream;
+  if (!grow_scratch(m->exit_scratch, m->exit_bytes, need, st)) return DEER_ERR_LAUNCH;
+  ScratchTake take{reinterpret_cast<char*>(m->exit_scratch)};
+  float* PW = P == nullptr ? take(n_p) : nullptr;
+  float* XS = take(2 * n_x);
+  float* XH = take(n_x);
+  if (P == nullptr) {
+    DEER_TRY(deer_pool_window_layers(m, (int)R, T, PW, stream));
+    P = PW;
+  }
+  DEER_TRY(deer_window_gather_layers(P, sel, slot_of, c.n_layers, XS, 2, bs, W, NE, d, stream));
+  const int flags = c.use_state ? DEER_SEQ_STATE : 0;
+  const long n_act = R * 8 * A;
+  int h = 0;
+  // one head on one layer's pooled rows: windows as sequences of single-row steps (pooling one row is the identity), zero state
+  auto head_on_layer = [&](int head, int slot) -> int {
+    if (hipMemcpy2DAsync(XH, (size_t)d * sizeof(float), P + (long)slot * d, (size_t)NE * d * sizeof(float), (size_t)d * sizeof(float), (size_t)R,
+                         hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return DEER_ERR_LAUNCH;
+    return deer_head_sequence_ex(m, head, XH, bs, W, 1, nullptr, nullptr, state, flags, actions + (long)(h++) * n_act, nullptr, nullptr, nullptr,
+                                 nullptr, stream);
+  };
+  // all_outputs order (train_utils.py:503): the internal exits' heads, the last layer's head (lm_head; extra_exit on a model built
+  // without per-layer heads), extra_exit on strategy 1, extra_exit on strategy 2
+  for (int k = 0; k + 1 < (int)m->lw.size(); ++k) DEER_TRY(head_on_layer(k + 1, slot_of[m->lw[k].layer]));
+  DEER_TRY(head_on_layer(m->lw.empty() ? 0 : (int)m->lw.size(), NE - 1));
+  for (int s = 0; s < 2; ++s)
+    DEER_TRY(deer_head_sequence_ex(m, 0, XS + (long)s * n_x, bs, W, 1, nullptr, nullptr, state, flags, actions + (long)(h++) * n_act, nullptr, nullptr,
+                                   nullptr, nullptr, stream));
+  return DEER_OK;
+}
+
+int deer_exit_n_heads(const deer_model* m) { return (m->lw.empty() ? 0 : (int)m->lw.size() - 1) + 3; }
+
+long deer_model_scratch_bytes(const deer_model* m) { return (long)(m->seq_bytes + m->calib_bytes + m->exit_bytes); }
 
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream) {
   if (m->ws == nullptr || T <= 0 || T > m->c.max_text_len || m->B * T > kMaxRows || exit_id >= m->c.n_layers) return DEER_ERR_SHAPE;

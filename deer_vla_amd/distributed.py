@@ -67,6 +67,25 @@ def _all_reduce_sum(packed: torch.Tensor, device=None) -> torch.Tensor:
     return t
 
 
+def pack_exit_losses(sums: torch.Tensor, count: int) -> torch.Tensor:
+    """Per-head (sum, count) pairs of the per-exit demonstration loss (evaluate.exit_losses_on_windows) as one float64 vector: the row count
+    followed by the per-head sums of num, bin and loss - sums (3, Hn).  Sums of rows reduce with one all_reduce(SUM)."""
+    s = sums.detach().to(device="cpu", dtype=torch.float64)
+    assert s.dim() == 2 and s.shape[0] == 3, s.shape
+    return torch.cat([torch.tensor([float(count)], dtype=torch.float64), s.reshape(-1)])
+
+
+def unpack_exit_losses(packed: torch.Tensor):
+    """inverse of pack_exit_losses: (sums (3, Hn) float64, count)"""
+    assert packed.dim() == 1 and (packed.numel() - 1) % 3 == 0, packed.shape
+    return packed[1:].reshape(3, -1).to(torch.float64), int(round(float(packed[0])))
+
+
+def reduce_exit_losses(sums: torch.Tensor, count: int, device=None):
+    """all_reduce(SUM) over the ranks of every head's (sum, count) pairs -> (sums (3, Hn), count) of the whole evaluation set"""
+    return unpack_exit_losses(_all_reduce_sum(pack_exit_losses(sums, count), device))
+
+
 def reduce_metrics(packed: torch.Tensor, device=None, n_extra: int = 0) -> Dict[str, float]:
     """all_reduce(SUM) over ranks (a few hundred bytes: latency-bound, xGMI bandwidth is irrelevant) -> metrics of
     ``print_and_save`` (eval_utils.py:71-118): avg successful length, chain success rates 1-5, avg exit layer (+1)."""

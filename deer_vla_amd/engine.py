@@ -601,6 +601,7 @@ class DeerEngine:
         ids = ids.reshape(B, -1)
         T = ids.shape[1]
         assert 0 < T <= self.max_T and B * T <= self.max_rows
+        self._last_T = T                                      # rows per environment of the hidden states the next step leaves (exit_outputs(None, ..))
         # the instruction only changes between sub-tasks: skip the upload when the caller hands over the same tensor again
         tag = (ids.data_ptr(), ids._version, B * T)
         if tag != self._ids_tag:
@@ -999,6 +1000,80 @@ class DeerEngine:
             f = f.unsqueeze(0)
         rl = torch.as_tensor(rand_layers).reshape(f.shape[0], -1)
         return run_calibrate_values(self.lib, self._h, self.cfg, self.exit_ids, f, rl, threshold_type, return_actions)
+
+    def window_exit_pooled(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8, hidden: bool = False):
+        """The grouped static full-depth window pass of ``window_hidden_states`` reduced to what the all-exits forward reads: the POOLED
+        feature (action_head.py:519-520, all T rows) of every exit layer ``cfg.exit_ids()``, (F, NE, d) fp32 on the device - each group ends
+        in one ``deer_pool_window_layers`` launch.  hidden=True also returns the (F, n_layers, T, d) hidden states (``output.hidden_states``
+        of the reference)."""
+        F = rgb_seq.shape[0]
+        ids = ids.reshape(-1, ids.shape[-1])
+        T = ids.shape[1]
+        G = max(1, min(group, self.MAX_ROWS // T, F, abi.MAX_ENVS))
+        last = self.cfg.n_layers - 1
+        L, d, NE = self.cfg.n_layers, self.cfg.d_model, len(self.cfg.exit_ids())
+        n_groups = (F + G - 1) // G
+        out = torch.empty(n_groups * G, NE, d, device=self.dev)    # whole groups: the padded frames of the last one are cut off below
+        hid = torch.empty(F, L, T, d, device=self.dev) if hidden else None
+        ws = [self.sibling(G)] + ([self.sibling(G, 1)] if n_groups > 1 else [])
+        cur = torch.cuda.current_stream()
+        sts = [cur] + ([self._side_stream] if n_groups > 1 else [])
+        for w in ws:
+            w._drain_side_streams()
+        if n_groups > 1:
+            self._side_stream.wait_stream(cur)                    # inputs produced on the caller's stream
+        for gi, f0 in enumerate(range(0, F, G)):
+            w, st = ws[gi % len(ws)], sts[gi % len(ws)]
+            with torch.cuda.stream(st):
+                idx = [min(f0 + i, F - 1) for i in range(G)]      # the last group is padded with its last frame
+                ids_g = ids[idx] if ids.shape[0] == F else ids.expand(G, T)
+                mask_g = None
+                if mask is not None:
+                    m2 = mask.reshape(-1, T)
+                    mask_g = m2[idx] if m2.shape[0] == F else m2.expand(G, T)
+                T_, use_mask = w.load_inputs(rgb_seq[idx], grip_seq[idx], ids_g.contiguous(), mask_g)
+                w.hold_dev.zero_()
+                w._enqueue_step(T_, use_mask, last)               # static full depth: every layer's output is kept
+                abi.check(w.lib.deer_pool_window_layers(w._h, G, T_, abi.ptr(out[f0:f0 + G]), _cur_stream()), "deer_pool_window_layers")
+                if hidden:
+                    n = min(G, F - f0)
+                    hid[f0:f0 + n].copy_(w.hidden[:, :G * T].view(L, G, T, d).permute(1, 0, 2, 3)[:n])
+        if n_groups > 1:
+            cur.wait_stream(self._side_stream)
+        return (out[:F], hid) if hidden else out[:F]
+
+    def exit_outputs(self, feats, rand_layers, two_layers, state=None) -> torch.Tensor:
+        """The all-exits window forward (flamingo_mpt.py:463-517) as ONE spine call (include/deer_model.h deer_exit_outputs): feats
+        (bs, W, NE, d) pooled features of the exit layers from ``window_exit_pooled`` - or None: the hidden states the engine's last static
+        full-depth step left in its workspace, its n_envs rows being ONE window's frames (rand_layers then gives W) -, rand_layers /
+        two_layers (bs, W) the exit layer of every step under sampling strategy 1 / 2, state (bs, W, 15) robot_obs rows of a use_state model
+        -> actions (Hn, bs, W, 8 A) ON THE DEVICE in the reference's ``all_outputs`` order (train_utils.py:503): per-layer heads (a
+        layerwise_exit_eval model), the last layer's head, extra_exit on strategy 1, extra_exit on strategy 2.  The engine's committed
+        LSTM state does not change."""
+        from .ops import run_exit_outputs
+        rl, tl = torch.as_tensor(rand_layers), torch.as_tensor(two_layers)
+        if feats is None:
+            if getattr(self, "_last_T", None) is None:
+                raise RuntimeError("exit_outputs(None, ...): no static window pass has left hidden states in this engine's workspace")
+            rl, tl = rl.reshape(1, -1), tl.reshape(1, -1)
+            if rl.shape[1] != self.B:
+                raise ValueError(f"exit_outputs(None, ...): the workspace holds {self.B} frames, rand_layers gives a window of {rl.shape[1]}")
+            f = torch.empty(1, self.B, len(self.cfg.exit_ids()), self.cfg.d_model, device=self.dev)
+            abi.check(self.lib.deer_pool_window_layers(self._h, self.B, self._last_T, abi.ptr(f), _cur_stream()), "deer_pool_window_layers")
+        else:
+            f = feats.to(device=self.dev)
+            if f.dim() == 3:
+                f = f.unsqueeze(0)
+            rl, tl = rl.reshape(f.shape[0], -1), tl.reshape(f.shape[0], -1)
+        return run_exit_outputs(self.lib, self._h, self.cfg, f, rl, tl, state)
+
+    def exit_losses(self, actions: torch.Tensor, pose, grip01, w_bin: float = 0.01):
+        """The loss terms of the multi-exit step's forward half (train_utils.py:519-540) as ONE device pass (deer_exit_losses): actions
+        (Hn, ..., 8 A) from ``exit_outputs``, pose labels (..., 6 A), gripper targets (..., A) in {0, 1} -> (num (Hn, R) Huber(delta = 1)
+        mean over the pose values, bin (Hn, R) BCE-with-logits mean over the A logits, loss (Hn,) = mean over the rows of num + w_bin bin),
+        all on the device; deterministic (fixed summation order)."""
+        from .ops import run_exit_losses
+        return run_exit_losses(self.lib, self.cfg, actions.to(device=self.dev), torch.as_tensor(pose), torch.as_tensor(grip01), w_bin)
 
     def _head_eval(self, feats: torch.Tensor, commit: bool) -> torch.Tensor:
         """One DeterministicDecoder step of all n_envs sequences on ``feats`` (n_envs*T, d) from the current LSTM state; commit=True

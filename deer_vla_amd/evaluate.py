@@ -1,0 +1,87 @@
+"""Per-exit demonstration loss: how good every exit head of a checkpoint is on recorded demonstration windows, without a simulator or a
+rollout - the forward half of the reference's multi-exit training step (robot_flamingo/train/train_utils.py:466-543) in ``eval()``: no
+gradient, no optimizer, no dropout.
+
+One batch is what the reference's CALVIN loader yields, by name:
+  images, gripper   (bs, W, 3, S, S) camera frames of bs windows of W = model.window_size steps
+  input_ids         (bs, T) one right-padded instruction per window (or (bs, W, T)); attention_mask the same shape, or absent
+  labels            (bs, W, 7) relative actions = 6 pose values + the gripper command in {-1, 1}; (bs, W, A, 7) with multi_step_action = A
+  state             (bs, W, 15) robot_obs rows (use_state models only)
+The frames go through ``MPTFlamingo.all_exit_actions`` (one static full-depth pass + ``DeerEngine.exit_outputs``), the losses through
+``DeerEngine.exit_losses``; the per-head sums stay on the device until the end.
+"""
+from __future__ import annotations
+
+from typing import Dict, Iterable, Optional, Sequence
+
+import torch
+
+from .distributed import reduce_exit_losses
+
+
+def split_labels(labels: torch.Tensor, multi_step_action: int = 1):
+    """train_utils.py:485 (+ the multi_step_action reshape of :468,510-514): labels (bs, W, 7) or (bs, W, A, 7) / (bs, W, A * 7) ->
+    (pose (bs, W, 6 A), grip01 (bs, W, A)): ``labels[..., :6]`` and the gripper command -1 / 1 as the BCE target ``(labels[..., 6:] + 1) // 2``."""
+    A = max(1, int(multi_step_action))
+    if labels.dim() < 3:
+        raise ValueError(f"labels must be (bs, W, 7) or (bs, W, A, 7), got {tuple(labels.shape)}")
+    bs, W = labels.shape[:2]
+    if labels[0, 0].numel() != 7 * A:
+        raise ValueError(f"labels {tuple(labels.shape)} do not hold 7 values for each of the {A} actions of a step")
+    lab = labels.reshape(bs, W, A, 7)
+    pose, grip = lab[..., :6], (lab[..., 6:] + 1) // 2
+    return pose.reshape(bs, W, 6 * A), grip.reshape(bs, W, A)
+
+
+def window_batch_inputs(batch: Dict[str, torch.Tensor], window_size: int):
+    """The harness's reshaping of one loader batch (train_utils.py:470-478): batch and sequence dimension merged, one instruction row per
+    frame -> the keywords of ``MPTFlamingo.all_exit_actions``."""
+    images, gripper = batch["images"], batch["gripper"]
+    bs, W = images.shape[:2]
+    if W != window_size:
+        raise ValueError(f"windows of {W} steps for a model with window_size {window_size}")
+    ids = batch["input_ids"]
+    mask = batch.get("attention_mask")
+
+    def per_frame(t):
+        if t is None:
+            return None
+        t = t.unsqueeze(1).repeat(1, W, 1) if t.dim() == 2 else t
+        return t.flatten(0, 1)
+    state = batch.get("state")
+    return dict(vision_x=images.unsqueeze(2).unsqueeze(2).flatten(0, 1), vision_gripper=gripper.unsqueeze(2).unsqueeze(2).flatten(0, 1),
+                lang_x=per_frame(ids), attention_mask=per_frame(mask),
+                state_tensor=state.unsqueeze(2).unsqueeze(2).flatten(0, 1) if state is not None else None)
+
+
+def exit_losses_on_windows(model, batches: Iterable[Dict[str, torch.Tensor]], w_bin: float = 0.01, generator: Optional[torch.Generator] = None,
+                           weights: Optional[Sequence[float]] = None, device=None) -> Dict[str, object]:
+    """Per-head means of num (Huber, delta = 1), bin (BCE with logits) and loss = num + w_bin bin (train_utils.py:519-540; w_bin 0.01, or
+    0.05 for real data) over every (window, step) row of ``batches``, heads in the reference's ``all_outputs`` order (:503): per-layer
+    heads, the last layer's head, extra_exit on sampling strategy 1, extra_exit on strategy 2.  ``total`` is the reference's weighted sum
+    of the per-head losses (get_exit_weights, :179-181,541-543: all ones unless ``weights`` is given).  The layer tables of the two
+    strategies are drawn per batch like the reference's (``generator`` seeds the torch draws).  With torch.distributed initialised the
+    per-head (sum, count) pairs of all ranks are summed by one all-reduce."""
+    e = model.engine
+    A = e.A
+    sums, count = None, 0
+    for batch in batches:
+        pose, grip01 = split_labels(batch["labels"], A)
+        acts = model.all_exit_actions(generator=generator, **window_batch_inputs(batch, model.window_size))[0]     # (Hn, bs, W, 8 A)
+        num, bin_, loss = e.exit_losses(acts, pose, grip01, w_bin)
+        R = num.shape[1]
+        s = torch.stack([num.sum(1, dtype=torch.float64), bin_.sum(1, dtype=torch.float64), loss.to(torch.float64) * R])    # stays on the device
+        sums = s if sums is None else sums + s
+        count += R
+    if sums is None:
+        raise ValueError("exit_losses_on_windows: no batches")
+    sums, count = reduce_exit_losses(sums, count, device)
+    means = sums / max(count, 1)
+    Hn = means.shape[1]
+    w = torch.ones(Hn, dtype=torch.float64) if weights is None else torch.as_tensor(list(weights), dtype=torch.float64)
+    if w.numel() != Hn:
+        raise ValueError(f"{w.numel()} exit weights for {Hn} heads")
+    n_layer_heads = Hn - 3
+    names = [f"exit{k}" for k in range(n_layer_heads)] + ["final", "extra", "extra2"]
+    return {"heads": names, "num": means[0].tolist(), "bin": means[1].tolist(), "loss": means[2].tolist(),
+            "total": float((means[2] * w).sum()), "rows": count, "w_bin": float(w_bin)}

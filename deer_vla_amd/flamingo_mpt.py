@@ -443,7 +443,55 @@ class MPTFlamingo(nn.Module):
         grip = torch.tensor([x[gk] for x in r]) if A == 1 else torch.stack([x[gk] for x in r])
         return torch.stack([x[pk] for x in r]), grip, exits
 
-    def _forward_window(self, vision_x, lang_x, attention_mask, vision_gripper, with_gripper_logits=False, generator=None, rand_layers=None):
+    def draw_exit_layers(self, bs: int, Wn: int, generator=None):
+        """The layer tables of the two sampling strategies, drawn on the host in the reference's order (flamingo_mpt.py:485-503):
+        ``torch.randint(0, n, (bs, W))`` (strategy 1: a random exit per (window, step)), then ``random.randint(1, W)`` and
+        ``torch.randint(0, n, (bs, 2))`` (strategy 2: one exit for the first prev_len steps of a window, another for the rest).  Returns
+        (rand_layers, two_layers), int64 (bs, W) exit LAYERS on the CPU."""
+        import random
+        exit_ids = torch.tensor(self.get_all_exit_idx())
+        n = len(exit_ids)
+        idx1 = torch.randint(0, n, (bs, Wn), generator=generator)                           # :486
+        prev_len = random.randint(1, Wn)                                                    # :500
+        idx2 = torch.randint(0, n, (bs, 2), generator=generator)                            # :501
+        idx2 = torch.cat([idx2[:, :1].expand(bs, prev_len), idx2[:, 1:].expand(bs, Wn - prev_len)], dim=1)     # :502
+        return exit_ids[idx1], exit_ids[idx2]
+
+    def _window_inputs(self, vision_x, lang_x, attention_mask, vision_gripper, state_tensor):
+        """(bs, frames, gripper frames, ids, mask, state (bs, W, S) or None) of a window-mode call: the batch rows are bs * window_size
+        frames, one instruction per row; the robot state as the harness hands it over (train_utils.py:470-475: (bs * W, 1, 1, 15))."""
+        e, cfg = self.engine, self.cfg
+        Wn = self.window_size
+        F = vision_x.shape[0]
+        if F % Wn:
+            raise NotImplementedError(f"window mode takes whole windows: {F} batch rows are not a multiple of window_size {Wn} (the reference "
+                                      "reshapes the batch into windows, flamingo_mpt.py:479)")
+        bs, S = F // Wn, cfg.image_size
+        T = lang_x.shape[-1]
+        state = None
+        if self.use_state:
+            if state_tensor is None:
+                raise ValueError("a use_state model needs state_tensor in window mode: (bs * window_size, 1, 1, 15) robot_obs rows (action_head.py:524-536)")
+            if state_tensor.numel() % F:
+                raise ValueError(f"state_tensor {tuple(state_tensor.shape)} does not hold one robot_obs row for each of the {F} frames")
+            state = state_tensor.reshape(bs, Wn, -1)
+        return (bs, vision_x.reshape(F, 3, S, S).to(e.dev, e.img_dtype), vision_gripper.reshape(F, 3, S, S).to(e.dev, e.img_dtype),
+                lang_x.reshape(F, T).to(e.dev), attention_mask.reshape(F, T).to(e.dev) if attention_mask is not None else None, state)
+
+    def _layer_table(self, layers, bs, name):
+        """an explicit layer table of a recorded reference call (parity tests): (bs, W) exit layers on the CPU"""
+        t = torch.as_tensor(layers).reshape(bs, self.window_size).long().cpu()
+        exit_ids = self.get_all_exit_idx()
+        assert all(int(v) in exit_ids for v in t.reshape(-1)), f"{name} must be exit layers"
+        return t
+
+    def _split_actions(self, a, with_gripper_logits):
+        A = self.engine.A
+        pose, grip, glog = a[..., :6 * A], a[..., 6 * A:7 * A], a[..., 7 * A:8 * A]
+        return (pose, (grip, glog)) if with_gripper_logits else (pose, grip)
+
+    def _forward_window(self, vision_x, lang_x, attention_mask, vision_gripper, with_gripper_logits=False, generator=None, rand_layers=None,
+                        state_tensor=None):
         """Window mode (flamingo_mpt.py:463-517 as ``generate_action_values`` calls it, value_net.py:375-385): the batch rows are
         bs * window_size frames (one instruction per row); every layer's hidden state is returned, the history fed to
         ``extra_exit`` comes from a random exit layer per (window, time step) ("sampling strategy 1", :485-497) and the head runs the
@@ -451,42 +499,66 @@ class MPTFlamingo(nn.Module):
         rand_layer_feat, rand_layer_indices) like the reference with ``return_in_feat=True``.  The head pools over ALL T rows of a
         right-padded instruction like the reference's (no mask reaches ``DeterministicDecoder``, action_head.py:519-520;
         tests/golden/deer_window_padded.npz).  The frames run as batch rows through
-        the env-batch engine (``DeerEngine.window_hidden_states``), the windows as the environments of the head evaluations."""
+        the env-batch engine (``DeerEngine.window_hidden_states``), the head as ONE ``head_sequence`` call over the windows."""
         e, cfg = self.engine, self.cfg
         Wn = self.window_size
-        F = vision_x.shape[0]
-        assert F % Wn == 0, f"window mode: {F} batch rows are not a multiple of window_size {Wn}"
-        bs, S = F // Wn, cfg.image_size
-        T = lang_x.shape[-1]
-        hid = e.window_hidden_states(vision_x.reshape(F, 3, S, S).to(e.dev, e.img_dtype),
-                                     vision_gripper.reshape(F, 3, S, S).to(e.dev, e.img_dtype), lang_x.reshape(F, T).to(e.dev),
-                                     attention_mask.reshape(F, T).to(e.dev) if attention_mask is not None else None)     # (F, L, T, d)
+        bs, rgb, grip_f, ids, mask, state = self._window_inputs(vision_x, lang_x, attention_mask, vision_gripper, state_tensor)
+        F, T = bs * Wn, ids.shape[-1]
+        hid = e.window_hidden_states(rgb, grip_f, ids, mask)                                # (F, L, T, d)
         hidden = tuple(hid[:, l] for l in range(cfg.n_layers))
         exit_ids = self.get_all_exit_idx()
         if rand_layers is None:
             idx = torch.randint(0, len(exit_ids), (bs, Wn), generator=generator)             # :485
             rand_layers = torch.tensor([exit_ids[int(i)] for i in idx.reshape(-1)]).reshape(bs, Wn)
         else:                                             # the history layers of a recorded reference call (parity tests)
-            rand_layers = torch.as_tensor(rand_layers).reshape(bs, Wn).long().cpu()
-            assert all(int(v) in exit_ids for v in rand_layers.reshape(-1)), "rand_layers must be exit layers"
+            rand_layers = self._layer_table(rand_layers, bs, "rand_layers")
         rand_feat = hid[torch.arange(F, device=hid.device), rand_layers.reshape(-1).to(hid.device)]      # (F, T, d)
-        # extra_exit on the random-layer features, windows as sequences from a zero LSTM state: groups of <= 8 windows per evaluation
-        G = max(1, min(8, e.MAX_ROWS // T, bs))   # groups of <= 8 windows per head evaluation
-        w = e.sibling(G)
-        rows = []
-        rf = rand_feat.view(bs, Wn, T, cfg.d_model)
-        for b0 in range(0, bs, G):
-            gidx = [min(b0 + i, bs - 1) for i in range(G)]
-            w.h_state.zero_()
-            w.c_state.zero_()
-            acts = [w._head_eval(rf[gidx, t].reshape(G * T, cfg.d_model).contiguous(), commit=True) for t in range(Wn)]
-            rows.append(torch.stack(acts, dim=1)[: min(G, bs - b0)])                        # (g, W, 8)
-        a = torch.cat(rows, dim=0)                                                          # (bs, W, 8)
-        A = e.A
-        pose, grip, glog = a[..., :6 * A], a[..., 6 * A:7 * A], a[..., 7 * A:8 * A]
-        extra = (pose, (grip, glog)) if with_gripper_logits else (pose, grip)
+        # extra_exit on the random-layer features, windows as sequences from a zero LSTM state
+        a = e.head_sequence(rand_feat.view(bs, Wn, T, cfg.d_model), state=state)[0]         # (bs, W, 8 A)
+        extra = self._split_actions(a, with_gripper_logits)
         out = CausalLMOutputWithPast(logits=extra, hidden_states=hidden, exit_layer=cfg.n_layers - 1)
         return out, [], extra, rand_feat, rand_layers.to(hid.device)
+
+    def all_exit_actions(self, vision_x, lang_x, attention_mask, vision_gripper, state_tensor=None, generator=None, rand_layers=None,
+                         two_layers=None, hidden: bool = False):
+        """The device side of the all-exits branch (flamingo_mpt.py:463-517): one grouped static full-depth pass that keeps the pooled
+        features of the exit layers, then ONE ``DeerEngine.exit_outputs`` call.  Returns (actions (Hn, bs, W, 8 A) on the device in the
+        reference's ``all_outputs`` order (train_utils.py:503), rand_layers, two_layers (bs, W) on the CPU, hidden states (F, L, T, d) or
+        None).  rand_layers / two_layers: the tables of a recorded reference call; default: drawn like the reference's."""
+        e = self.engine
+        Wn = self.window_size
+        bs, rgb, grip_f, ids, mask, state = self._window_inputs(vision_x, lang_x, attention_mask, vision_gripper, state_tensor)
+        if self.use_state and self.layerwise_exit_eval:
+            raise NotImplementedError("layerwise_exit_eval with use_state is not built (the per-layer heads would need their own state embeddings)")
+        if rand_layers is None or two_layers is None:
+            d1, d2 = self.draw_exit_layers(bs, Wn, generator)
+            rand_layers = d1 if rand_layers is None else rand_layers
+            two_layers = d2 if two_layers is None else two_layers
+        rand_layers, two_layers = self._layer_table(rand_layers, bs, "rand_layers"), self._layer_table(two_layers, bs, "two_layers")
+        pooled = e.window_exit_pooled(rgb, grip_f, ids, mask, hidden=hidden)
+        hid = None
+        if hidden:
+            pooled, hid = pooled
+        acts = e.exit_outputs(pooled.view(bs, Wn, pooled.shape[1], pooled.shape[2]), rand_layers, two_layers, state=state)
+        return acts, rand_layers, two_layers, hid
+
+    def _forward_all_exits(self, vision_x, lang_x, attention_mask, vision_gripper, state_tensor=None, with_gripper_logits=False,
+                           return_in_feat=False, generator=None, rand_layers=None, two_layers=None):
+        """"output actions by all exits" (flamingo_mpt.py:463-517) in the reference's layout: (output, exit_outputs, extra_exit_output,
+        extra_exit_output2), or with ``return_in_feat`` (output, exit_outputs, extra_exit_output, rand_layer_feat, rand_layer_indices).
+        ``output.logits`` is the last layer's head (lm_head; extra_exit's weights on a model built without per-layer heads, whose
+        ``exit_outputs`` is empty), each output (pose (bs, W, 6 A), gripper (bs, W, A)) or (pose, (gripper, logits))."""
+        cfg = self.cfg
+        acts, rand_layers, two_layers, hid = self.all_exit_actions(vision_x, lang_x, attention_mask, vision_gripper, state_tensor, generator,
+                                                                   rand_layers, two_layers, hidden=True)
+        outs = [self._split_actions(acts[h], with_gripper_logits) for h in range(acts.shape[0])]
+        exit_outputs, final, extra, extra2 = outs[:-3], outs[-3], outs[-2], outs[-1]
+        hidden = tuple(hid[:, l] for l in range(cfg.n_layers))
+        out = CausalLMOutputWithPast(logits=final, hidden_states=hidden, exit_layer=cfg.n_layers - 1)
+        if return_in_feat:
+            rand_feat = hid[torch.arange(hid.shape[0], device=hid.device), rand_layers.reshape(-1).to(hid.device)]       # (F, T, d)
+            return out, exit_outputs, extra, rand_feat, rand_layers.to(hid.device)
+        return out, exit_outputs, extra, extra2
 
     def forward(self, vision_x: torch.Tensor, lang_x: torch.Tensor, attention_mask: torch.Tensor = None, labels=None,
                 use_cached_vision_x: bool = False, clear_conditioned_layers: bool = True, past_key_values=None,
@@ -502,14 +574,14 @@ class MPTFlamingo(nn.Module):
         if vision_x.ndim != 6 or vision_x.shape[1] != 1:
             raise NotImplementedError("vision_x must be (B, 1, 1, 3, S, S)")
         assert vision_x.shape[2] == 1, "Only single frame supported"
-        if self.use_state and exit_id is None and not (dynamic_early_exit and exit_controller is not None):
-            raise NotImplementedError("window-mode calibration with use_state is not implemented")
         if exit_id is None and not (dynamic_early_exit and exit_controller is not None):
-            # the all-exits branch (flamingo_mpt.py:463-517): inference-side use = window-mode calibration (value_net.py:375-385)
-            if not (only_extra_exit and return_in_feat):
-                raise NotImplementedError("the training losses of the all-exits branch are out of scope; the calibration call "
-                                          "(only_extra_exit=True, return_in_feat=True, value_net.py:375-385) is supported")
-            return self._forward_window(vision_x, lang_x, attention_mask, vision_gripper, with_gripper_logits)
+            # the all-exits branch (flamingo_mpt.py:463-517) in eval(): the calibration call (only_extra_exit=True, return_in_feat=True,
+            # value_net.py:375-385) and the forward half of the multi-exit step (train_utils.py:487-503); no gradient, no dropout
+            if only_extra_exit:
+                if not return_in_feat:
+                    raise NotImplementedError("only_extra_exit is the calibration call (value_net.py:375-385): pass return_in_feat=True")
+                return self._forward_window(vision_x, lang_x, attention_mask, vision_gripper, with_gripper_logits, state_tensor=state_tensor)
+            return self._forward_all_exits(vision_x, lang_x, attention_mask, vision_gripper, state_tensor, with_gripper_logits, return_in_feat)
         if vision_x.shape[0] != 1:
             raise NotImplementedError("step mode takes one frame pair (B=1); batches of frames go through the window-mode call")
         if self.use_state and exit_id is None:

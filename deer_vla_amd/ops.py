@@ -299,6 +299,100 @@ def run_calibrate_values(lib, handle, cfg, exit_ids, feats: torch.Tensor, rand_l
     return (values, actions) if return_actions else values
 
 
+def exit_head_count(cfg) -> int:
+    """Heads of the all-exits forward in the reference's ``all_outputs`` order (train_utils.py:503): one per internal exit when the model
+    carries per-layer heads (layerwise_exit_eval), the last layer's head, extra_exit on sampling strategy 1 and on strategy 2."""
+    return (len(cfg.exit_ids()) - 1 if getattr(cfg, "layerwise_exit_eval", False) else 0) + 3
+
+
+def exit_outputs_shapes(cfg, feats_shape, rand_layers, two_layers, state=None):
+    """Host-side checks of an all-exits call (no device touched): feats (bs, W, NE, d) pooled features of the exit layers
+    ``cfg.exit_ids()`` (flamingo_mpt.py:268-270), rand_layers / two_layers (bs, W) the exit LAYER of every step under sampling strategy
+    1 / 2 (checked here when they live on the host; on the device a layer that is no exit makes its window's actions NaN), state
+    (bs, W, S) / (bs * W, S) robot_obs rows (use_state models only).  Returns (bs, W, NE, Hn, A)."""
+    exits = [int(e) for e in cfg.exit_ids()]
+    NE = len(exits)
+    if len(feats_shape) != 4:
+        raise ValueError(f"exit_outputs: feats must be (bs, W, NE, d), got {tuple(feats_shape)}")
+    bs, W, ne, d = (int(v) for v in feats_shape)
+    if bs < 1 or W < 1:
+        raise ValueError(f"exit_outputs: needs bs >= 1 windows of W >= 1 steps, got bs = {bs}, W = {W}")
+    if ne != NE or d != cfg.d_model:
+        raise ValueError(f"exit_outputs: feats (bs, W, NE, d) = {tuple(feats_shape)} for the {NE} exit layers {exits} and d_model {cfg.d_model}")
+    for name, t in (("rand_layers", rand_layers), ("two_layers", two_layers)):
+        if tuple(t.shape) != (bs, W):
+            raise ValueError(f"exit_outputs: {name} must be (bs, W) = {(bs, W)}, got {tuple(t.shape)}")
+        if t.device.type == "cpu":
+            bad = [int(v) for v in t.reshape(-1).tolist() if int(v) not in exits]
+            if bad:
+                raise ValueError(f"exit_outputs: {name} holds {sorted(set(bad))}, not exit layers {exits}")
+    if getattr(cfg, "use_state", False):
+        if state is None:
+            raise ValueError("exit_outputs: a use_state model needs the robot state of every step (state_tensor, action_head.py:524-536)")
+        if state.numel() % (bs * W) or state.numel() // (bs * W) < 7:
+            raise ValueError(f"exit_outputs: state {tuple(state.shape)} does not hold one robot_obs row per (window, step) of {bs} x {W}")
+    elif state is not None:
+        raise ValueError("exit_outputs: state given to a model without use_state")
+    return bs, W, NE, exit_head_count(cfg), max(1, int(getattr(cfg, "multi_step_action", 1)))
+
+
+def run_exit_outputs(lib, handle, cfg, feats: torch.Tensor, rand_layers, two_layers, state=None) -> torch.Tensor:
+    """One ``deer_exit_outputs`` call on the current stream: actions (Hn, bs, W, 8 A) on the device."""
+    rl, tl = torch.as_tensor(rand_layers), torch.as_tensor(two_layers)
+    bs, W, NE, Hn, A = exit_outputs_shapes(cfg, feats.shape, rl, tl, state)
+    dev = feats.device
+    f = feats.to(torch.float32).contiguous()
+    sel = torch.stack([rl.to(device=dev, dtype=torch.int32), tl.to(device=dev, dtype=torch.int32)]).contiguous()
+    st = None
+    if state is not None:                       # (arm pose robot_obs[:6], gripper robot_obs[-1], pad) per row, like "state_in"
+        s2 = state.reshape(bs * W, -1).to(device=dev, dtype=torch.float32)
+        st = torch.zeros(bs * W, 8, dtype=torch.float32, device=dev)
+        st[:, :6] = s2[:, :6]
+        st[:, 6] = s2[:, -1]
+    assert lib.deer_exit_n_heads(handle) == Hn
+    actions = torch.empty(Hn, bs, W, 8 * A, dtype=torch.float32, device=dev)
+    abi.check(lib.deer_exit_outputs(handle, abi.ptr(f), 1, abi.ptr(sel), abi.ptr(st), bs, W, abi.ptr(actions), _stream()), "deer_exit_outputs")
+    return actions
+
+
+def exit_losses_shapes(cfg, actions_shape, pose_shape, grip_shape):
+    """Host-side checks of a loss call: actions (Hn, ..., 8 A) with R rows per head, pose labels R x 6 A, gripper targets R x A (0 / 1).
+    Returns (Hn, R, A)."""
+    A = max(1, int(getattr(cfg, "multi_step_action", 1)))
+    if len(actions_shape) < 2 or int(actions_shape[-1]) != 8 * A:
+        raise ValueError(f"exit_losses: actions must be (Hn, ..., 8 A = {8 * A}), got {tuple(actions_shape)}")
+    Hn = int(actions_shape[0])
+    R = 1
+    for v in actions_shape[1:-1]:
+        R *= int(v)
+    if Hn < 1 or R < 1:
+        raise ValueError(f"exit_losses: no heads / rows in actions {tuple(actions_shape)}")
+    n_pose, n_grip = 1, 1
+    for v in pose_shape:
+        n_pose *= int(v)
+    for v in grip_shape:
+        n_grip *= int(v)
+    if n_pose != R * 6 * A or n_grip != R * A:
+        raise ValueError(f"exit_losses: labels pose {tuple(pose_shape)} / gripper {tuple(grip_shape)} do not hold {6 * A} / {A} values for each of "
+                         f"the {R} rows of actions {tuple(actions_shape)}")
+    return Hn, R, A
+
+
+def run_exit_losses(lib, cfg, actions: torch.Tensor, pose, grip01, w_bin: float = 0.01):
+    """One ``deer_exit_losses`` call on the current stream: (num (Hn, R), bin (Hn, R), loss (Hn,)) on the device."""
+    Hn, R, A = exit_losses_shapes(cfg, actions.shape, pose.shape, grip01.shape)
+    dev = actions.device
+    a = actions.to(torch.float32).contiguous()
+    p = pose.to(device=dev, dtype=torch.float32).contiguous()
+    g = grip01.to(device=dev, dtype=torch.float32).contiguous()
+    num = torch.empty(Hn, R, dtype=torch.float32, device=dev)
+    bin_ = torch.empty(Hn, R, dtype=torch.float32, device=dev)
+    loss = torch.empty(Hn, dtype=torch.float32, device=dev)
+    abi.check(lib.deer_exit_losses(abi.ptr(a), abi.ptr(p), abi.ptr(g), Hn, R, A, float(w_bin), abi.ptr(num), abi.ptr(bin_), abi.ptr(loss), _stream()),
+              "deer_exit_losses")
+    return num, bin_, loss
+
+
 @torch.library.custom_op("deer::calibrate_values", mutates_args=(), device_types="cuda")
 def calibrate_values(feats: torch.Tensor, rand_layers: torch.Tensor, model: int, threshold_type: str) -> torch.Tensor:
     """feats (bs, W, NL, d) pooled features of the candidate layers [0] + exits (deer_pool_exit_layers), rand_layers (bs, W) int -> the

@@ -432,6 +432,26 @@ int deer_calib_lstm_step(const float* pre, long ld_pre, const float* h_prev, lon
                          const float* zero_row, const void* w_hh, int w_kind, const float* b_hh, float* c_out, long ld_co, float* h_out,
                          long ld_out, int N, int H, void* stream);
 int deer_calib_delta(const float* actions, long ld_act, int NL, int rows, int NP, int thr_type, float* values, long ld_val, void* stream);
+/* ---- per-exit demonstration loss (csrc/exit_eval.hip): the all-exits window forward and the forward half of the multi-exit step ----
+ * Pieces that deer_exit_outputs (deer_model.h) chains with deer_calib_pool_layers (the pooling of an arbitrary host list of layers: reused,
+ * there is no second pooling kernel) and the window-mode head above.
+ * deer_window_gather_layers  the layer mixing of the two sampling strategies (robot_flamingo/models/flamingo_mpt.py:485-490 and :499-505)
+ *                            on POOLED rows (pooling, action_head.py:519-520, commutes with the per-step layer choice):
+ *                            X[s][(b, t)] = P[(b, t)][slot_of_layer[sel[s][b][t]]], all S selections in one launch.  P [bs W][NL][d];
+ *                            sel: DEVICE int32 [S][bs][W] exit layers; slot_of_layer: HOST int[n_layers] (-1: no slot -> NaN row, as
+ *                            deer_calib_gather).  d % 4 == 0 (16-byte loads and stores).
+ * deer_exit_losses           robot_flamingo/train/train_utils.py:519-540 for Hn heads over R = bs W rows: actions [Hn][R][8 A] = [pose 6 A |
+ *                            prob A | logit A], labels pose [R][6 A] and grip01 [R][A] ->
+ *                              num[h][r]  = F.huber_loss(pose, label, reduction='none').mean(-1), delta = 1           (:520)
+ *                              bin[h][r]  = F.binary_cross_entropy_with_logits(logit, grip01, reduction='none').mean(-1), computed as
+ *                                           max(x, 0) - x y + log1p(exp(-|x|))                                         (:529)
+ *                              loss[h]    = mean over r of num + w_bin bin (w_bin 0.01, or 0.05 for real data)          (:534-540)
+ *                            No atomics: per head one workgroup sums its rows in a fixed order.  The exit weighting (get_exit_weights,
+ *                            :541) is the caller's, from loss[h]. */
+int deer_window_gather_layers(const float* P, const int* sel, const int* slot_of_layer, int n_layers, float* X, int S, int bs, int W, int NL,
+                              int d, void* stream);
+int deer_exit_losses(const float* actions, const float* pose, const float* grip01, int Hn, long R, int A, float w_bin, float* num, float* bin,
+                     float* loss, void* stream);
 /* ExitController.set_timestep (eval_utils.py:662-663) + per-step reset.  step_info: device int32[4] = {hold, step sequence
  * number, host mirror pointer lo, hi} or NULL (no stage hold, no mirror). */
 int deer_ctl_begin_step(int* ctl, const int* step_info, int B, void* stream);

@@ -191,6 +191,31 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
 int deer_pool_exit_layers(deer_model* m, int n_frames, int T, float* P, void* stream);
 int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers, int bs, int W, int threshold_type, float* values,
                           float* actions, void* stream);
+/* The all-exits window forward (robot_flamingo/models/flamingo_mpt.py:463-517, "output actions by all exits") on the device, the
+ * counterpart of deer_pool_exit_layers + deer_calibrate_values for the per-exit demonstration loss (train_utils.py:487-543, forward half).
+ * The exit layers E = get_all_exit_idx (flamingo_mpt.py:268-270: every exit_interval-th layer below the last one + the last one; NE of
+ * them) carry the per-layer heads, end in the last layer and are what both sampling strategies draw from.
+ * deer_pool_window_layers  after a static full-depth step of n_frames frames (batch rows) of T tokens: P [n_frames][NE][d] = the pooled
+ *                          feature (action_head.py:519-520, max / mean over all T rows) of hidden_states[E[k]].  One launch of
+ *                          deer_calib_pool_layers (deer_hip.h), which takes any host list of layers.
+ * deer_exit_outputs        every head of the reference's `all_outputs` (train_utils.py:503) over bs windows of W steps, each from a zero
+ *                          state with the windows as sequences (action_head.py:588-595):
+ *   P        device f32 [bs][W][NE][d] pooled features, or NULL: pool the workspace's hidden states of the last static pass (bs W <= n_envs
+ *            frames of T tokens) first
+ *   sel      device int32 [2][bs][W]: the exit LAYER of every step under sampling strategy 1 (flamingo_mpt.py:486-490) and 2 (:500-505); a
+ *            layer outside E gives NaN actions for its window
+ *   state    device f32 [bs][W][8] (robot_obs[:6], robot_obs[-1], pad) on a use_state model - it reaches every head, as the reference
+ *            hands state_tensor to all of them (:465,472,493,508) -, else NULL
+ *   actions  device f32 [Hn][bs][W][8 A] = [pose 6 A | gripper prob A | logit A], Hn = deer_exit_n_heads, in the order: per-layer head
+ *            k on E[k] for every internal exit (models built with layerwise_exit_eval), the last layer's head (lm_head; extra_exit on a
+ *            model without per-layer heads), extra_exit on strategy 1, extra_exit on strategy 2
+ * Each head is deer_head_sequence's schedule on single-row steps (pooling one row is the identity): more than 2048 rows run in chunks of
+ * whole windows, a row's result does not depend on the chunking.  The model's LSTM state, control blocks and workspace are not touched;
+ * scratch as deer_head_sequence.  DEER_ERR_SHAPE: bad argument, state missing on / given without use_state, more than
+ * DEER_CALIB_MAX_NL exit layers. */
+int deer_pool_window_layers(deer_model* m, int n_frames, int T, float* P, void* stream);
+int deer_exit_outputs(deer_model* m, const float* P, int T, const int* sel, const float* state, int bs, int W, float* actions, void* stream);
+int deer_exit_n_heads(const deer_model* m);
 long deer_model_scratch_bytes(const deer_model* m);
 /* whole control step on ONE stream (vision batched): begin + vision + media K/V + trunk + heads */
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream);
