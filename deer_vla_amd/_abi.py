@@ -164,6 +164,8 @@ SIGNATURES = {
     "deer_pool_window_layers": [P, I, I, P, P],
     "deer_exit_outputs": [P, P, I, P, P, I, I, P, P],
     "deer_exit_n_heads": [P],
+    # exit thresholds of many operating points in one launch (csrc/thresholds.hip)
+    "deer_solve_thresholds": [P, I, I, I, P, I, I, I, P, P, P, P, P],
     "deer_model_scratch_bytes": [P],
     "deer_model_n_chains": [P],
     "deer_prof_enable": [P, I],

@@ -1001,6 +1001,18 @@ class DeerEngine:
         rl = torch.as_tensor(rand_layers).reshape(f.shape[0], -1)
         return run_calibrate_values(self.lib, self._h, self.cfg, self.exit_ids, f, rl, threshold_type, return_actions)
 
+    def solve_thresholds(self, values: torch.Tensor, counts, leq: bool = True, return_status: bool = False):
+        """The threshold solver of ``ExitController.set_threshold`` (value_net.py:242-262) for k operating points as ONE launch
+        (deer_solve_thresholds, csrc/thresholds.hip): values (n_stage, n_sample) f32 from ``calibrate_values`` (used where it lies: a column
+        slice of a wider matrix is fine), counts (k, n_exit) ints - ``value_net.exit_counts`` of every point, host or device -> (thresholds
+        (k, n_exit) f32, exit_counts (k, n_exit) i32 - the samples of the calibration set that leave at every exit) ON THE DEVICE; nothing
+        is synchronised and the scratch (k * n_sample bytes) is taken here.  A threshold row padded to 16 with 1e8 is what
+        ``set_thresholds_device`` / ``set_env_exit`` take.  return_status=True adds status (k,) i32, the NaNs the kernel met per point:
+        callers that read the results to the host check it (``value_net.controllers_from_values(engine=...)``, ``solve_for_budget``)."""
+        from .ops import run_solve_thresholds
+        T, left, status = run_solve_thresholds(self.lib, values.to(device=self.dev), counts, leq)
+        return (T, left, status) if return_status else (T, left)
+
     def window_exit_pooled(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8, hidden: bool = False):
         """The grouped static full-depth window pass of ``window_hidden_states`` reduced to what the all-exits forward reads: the POOLED
         feature (action_head.py:519-520, all T rows) of every exit layer ``cfg.exit_ids()``, (F, NE, d) fp32 on the device - each group ends

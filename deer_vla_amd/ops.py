@@ -13,6 +13,10 @@ through PyTorch-ROCm custom ops").  These are the three coarse operators SURVEY.
   deer::calibrate_values(Tensor feats, Tensor rand_layers, int model, str threshold_type) -> Tensor values
                                                                                ActionValueNet.forward(mode='generate')
                                                                                (value_net.py:134-160) on pooled exit-layer features
+  deer::solve_thresholds(Tensor values, Tensor counts, bool leq) -> (Tensor thresholds, Tensor exit_counts, Tensor status)
+                                                                               the solver of ExitController.set_threshold
+                                                                               (value_net.py:242-262), k operating points per launch;
+                                                                               model-free (no ``model`` argument)
 
 ``model`` is the address of a ``deer_model`` (``NativeModel.handle``): weights, workspace, LSTM state and the exit controller
 configuration live in that object, like they live in the reference's stateful ``MPTFlamingo`` module.
@@ -406,6 +410,60 @@ def _(feats, rand_layers, model, threshold_type):
     m = _model(model)
     bs, W, NL, S, _ = calibrate_shapes(m.cfg, m.exit_ids, feats.shape, rand_layers, threshold_type)
     return feats.new_empty((NL - 1, bs * S), dtype=torch.float32)
+
+
+def solve_thresholds_shapes(values, counts):
+    """Host-side checks of a threshold solve (no device touched): values (n_stage, n_sample) float32 deltas of the calibration set,
+    counts (k, n_exit) integers - ``value_net.exit_counts`` of every operating point; the solver reads rows 0 .. n_exit - 2 of values.
+    Returns (n_stage, n_sample, k, n_exit)."""
+    if values.dim() != 2 or values.dtype != torch.float32:
+        raise ValueError(f"solve_thresholds: values must be (n_stage, n_sample) float32, got {tuple(values.shape)} {values.dtype}")
+    n_stage, n_sample = (int(v) for v in values.shape)
+    if counts.dim() != 2 or counts.dtype.is_floating_point or counts.dtype == torch.bool:
+        raise ValueError(f"solve_thresholds: counts must be (k, n_exit) integers, got {tuple(counts.shape)} {counts.dtype}")
+    k, n_exit = (int(v) for v in counts.shape)
+    if k < 1 or n_exit < 1 or n_sample < 1:
+        raise ValueError(f"solve_thresholds: needs k >= 1 points, n_exit >= 1 exits and n_sample >= 1 samples, got values {tuple(values.shape)}, "
+                         f"counts {tuple(counts.shape)}")
+    if n_exit > 16:
+        raise ValueError(f"solve_thresholds: {n_exit} exits, a threshold row holds at most 16")
+    if n_exit > n_stage:
+        raise ValueError(f"solve_thresholds: counts for {n_exit} exits, values has {n_stage} rows")
+    return n_stage, n_sample, k, n_exit
+
+
+def run_solve_thresholds(lib, values: torch.Tensor, counts, leq: bool = True):
+    """One ``deer_solve_thresholds`` launch on the current stream: (thresholds (k, n_exit) f32, exit_counts (k, n_exit) i32, status (k,)
+    i32 - the NaNs met per point) on the device, nothing synchronised.  values stays where it is: a row stride above n_sample (a column
+    slice of a wider matrix) is passed on as ``ld``."""
+    counts = torch.as_tensor(counts)
+    n_stage, n_sample, k, n_exit = solve_thresholds_shapes(values, counts)
+    dev = values.device
+    v = values.detach()
+    if v.stride(1) != 1 or v.stride(0) < n_sample or v.stride(0) > 0x7fffffff:
+        v = v.contiguous()
+    c = counts.to(device=dev, dtype=torch.int32).contiguous()
+    alive = torch.empty(k * n_sample, dtype=torch.uint8, device=dev)
+    T = torch.empty(k, n_exit, dtype=torch.float32, device=dev)
+    left = torch.empty(k, n_exit, dtype=torch.int32, device=dev)
+    status = torch.empty(k, dtype=torch.int32, device=dev)
+    abi.check(lib.deer_solve_thresholds(abi.ptr(v), n_stage, n_sample, v.stride(0), abi.ptr(c), k, n_exit, 1 if leq else 0, abi.ptr(alive), abi.ptr(T),
+                                        abi.ptr(left), abi.ptr(status), _stream()), "deer_solve_thresholds")
+    return T, left, status
+
+
+@torch.library.custom_op("deer::solve_thresholds", mutates_args=(), device_types="cuda")
+def solve_thresholds(values: torch.Tensor, counts: torch.Tensor, leq: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """values (n_stage, n_sample) f32, counts (k, n_exit) int -> (thresholds (k, n_exit) f32, exit_counts (k, n_exit) i32, status (k,) i32):
+    the solver of ExitController.set_threshold (value_net.py:242-262) for k operating points in one launch (csrc/thresholds.hip)."""
+    return run_solve_thresholds(abi.lib(), values, counts, leq)
+
+
+@solve_thresholds.register_fake
+def _(values, counts, leq):
+    _, _, k, n_exit = solve_thresholds_shapes(values, counts)
+    return (values.new_empty((k, n_exit), dtype=torch.float32), values.new_empty((k, n_exit), dtype=torch.int32),
+            values.new_empty((k,), dtype=torch.int32))
 
 
 def decode_ctl(ctl: torch.Tensor):

@@ -17,17 +17,12 @@ from typing import List, Optional, Sequence
 import torch
 
 
-def solve_thresholds(values: torch.Tensor, real_num_exit: int, exit_ratio: float, exit_dist: str = "exp",
-                     leq: bool = True, model_name: str = "mpt_dolly_3b") -> torch.Tensor:
-    """Threshold solver of ``ExitController.set_threshold`` (value_net.py:203-260), vectorised.
-
-    values: (n_stage, n_sample) deltas gathered over the calibration set.  For every exit k (except the last)
-    the threshold is the value of the ``floor(n * probs[k])``-th not-yet-exited sample in sorted order, after
-    which every sample with value <= T[k] counts as exited.  probs ~ exit_ratio**k ('exp'), gaussian or gamma.
-    """
-    values = values.detach().to("cpu", torch.float32)
-    n_stage, n_sample = values.shape
-    T = torch.full((real_num_exit,), -1e8 if leq else 1e8, dtype=torch.float32)
+def exit_counts(n_sample: int, real_num_exit: int, exit_ratio: float, exit_dist: str = "exp",
+                model_name: str = "mpt_dolly_3b") -> List[int]:
+    """How many calibration samples every exit is to take (value_net.py:214-244): ``floor(n_sample * probs[k])`` with probs ~
+    exit_ratio**k ('exp'), gaussian or gamma, normalised, in the reference's f32 torch arithmetic - the one place where these integers
+    come from, for the host solver and for the device solver (``DeerEngine.solve_thresholds``) alike.  Returns real_num_exit ints; the
+    last exit takes whoever is left, its entry is 0 and no solver reads it."""
     if exit_dist == "exp":
         probs = torch.tensor([float(exit_ratio) ** k for k in range(1, real_num_exit + 1)], dtype=torch.float32)
     elif exit_dist == "gauss":
@@ -41,18 +36,72 @@ def solve_thresholds(values: torch.Tensor, real_num_exit: int, exit_ratio: float
     if "mpt_9b" in model_name:
         probs[0] = 0                     # value_net.py:235-236
     probs = probs / probs.sum()
+    return [math.floor(n_sample * probs[k]) for k in range(real_num_exit - 1)] + [0]
+
+
+def solve_from_counts(values: torch.Tensor, counts: Sequence[int], leq: bool = True):
+    """The selection loop of ``ExitController.set_threshold`` (value_net.py:242-262) for given counts (``exit_counts``), on the host:
+    for every exit k but the last the threshold is the value of the counts[k]-th not-yet-exited sample of values[k] in sorted order,
+    after which every sample with value <= T[k] (>= for not leq) counts as exited.  Returns (T (n_exit,) f32, the number of samples
+    that left at every exit - the last one's are those still alive)."""
+    values = values.detach().to("cpu", torch.float32)
+    real_num_exit, n_sample = len(counts), values.shape[1]
+    T = torch.full((real_num_exit,), -1e8 if leq else 1e8, dtype=torch.float32)
     filtered = torch.zeros(n_sample, dtype=torch.bool)
+    left = []
     for k in range(real_num_exit - 1):
-        out_n = math.floor(n_sample * probs[k])
+        out_n = counts[k]
         order = values[k].argsort(descending=not leq, stable=True)
         alive = ~filtered[order]
         rank = alive.cumsum(0)
         hit = (alive & (rank == out_n)).nonzero()
         if out_n > 0 and hit.numel() > 0:
             T[k] = values[k][order[hit[0, 0]]]
+        before = int(filtered.sum())
         filtered |= (values[k] <= T[k]) if leq else (values[k] >= T[k])
+        left.append(int(filtered.sum()) - before)
     T[real_num_exit - 1] = 1e8 if leq else -1e8
-    return T
+    return T, left + [n_sample - int(filtered.sum())]
+
+
+def solve_thresholds(values: torch.Tensor, real_num_exit: int, exit_ratio: float, exit_dist: str = "exp",
+                     leq: bool = True, model_name: str = "mpt_dolly_3b") -> torch.Tensor:
+    """Threshold solver of ``ExitController.set_threshold`` (value_net.py:203-260), vectorised.
+
+    values: (n_stage, n_sample) deltas gathered over the calibration set.  For every exit k (except the last)
+    the threshold is the value of the ``floor(n * probs[k])``-th not-yet-exited sample in sorted order, after
+    which every sample with value <= T[k] counts as exited.  probs ~ exit_ratio**k ('exp'), gaussian or gamma.
+    """
+    return solve_from_counts(values, exit_counts(values.shape[1], real_num_exit, exit_ratio, exit_dist, model_name), leq)[0]
+
+
+def _solve_points(values: torch.Tensor, counts: Sequence[Sequence[int]], leq: bool, engine=None):
+    """Thresholds and exit mixes of k points with the same number of exits: rows of floats, rows of ints.  With an engine and device
+    values: ONE ``DeerEngine.solve_thresholds`` call and ONE read of its k x (2 n_exit + 1) words, after which the kernel's NaN count is
+    checked; else the host solver, point by point."""
+    if engine is None or not values.is_cuda:
+        solved = [solve_from_counts(values[: len(c)], c, leq) for c in counts]
+        return [t.tolist() for t, _ in solved], [n for _, n in solved]
+    k, n_exit = len(counts), len(counts[0])
+    T, left, status = engine.solve_thresholds(values, torch.tensor(counts, dtype=torch.int32), leq, return_status=True)
+    words = torch.cat([T.view(torch.int32).reshape(-1), left.reshape(-1), status]).cpu()
+    if int(words[2 * k * n_exit:].sum()) != 0:
+        raise ValueError("NaN in calibration values")
+    return (words[: k * n_exit].view(torch.float32).view(k, n_exit).tolist(),
+            words[k * n_exit: 2 * k * n_exit].view(k, n_exit).tolist())
+
+
+def predicted_exit_mix(exit_counts: Sequence[int], exit_id_list: Sequence[int]):
+    """(fractions, average_exit_layer) of an operating point ON THE CALIBRATION SET: exit_counts[e] samples of the calibration matrix
+    leave at exit ``exit_id_list[e]`` under the solved thresholds, so the average is sum(count_e * (exit_id_e + 1)) / n_sample layers
+    (the "average exit layer" the reference's bayesian_optimization.py:75-79 names as its budget).  This is what the calibration samples
+    predict, not an on-policy promise: in a rollout the LSTM history comes from the exits actually taken, and VERDICT.md weak #11 records
+    that the two differ on the synthetic episodes."""
+    counts = [int(c) for c in exit_counts]
+    n_sample = sum(counts)
+    if len(counts) > len(exit_id_list) or n_sample < 1:
+        raise ValueError(f"{len(counts)} exit counts (sum {n_sample}) for the exits {list(exit_id_list)}")
+    return [c / n_sample for c in counts], sum(c * (int(e) + 1) for c, e in zip(counts, exit_id_list)) / n_sample
 
 
 class ActionValueNet:
@@ -146,8 +195,13 @@ class ExitController:
         self.thresholds = {self.exit_id_list[i]: float(thresholds[i]) for i in range(self.real_num_exit)}
         self._version += 1
 
-    def set_threshold_from_values(self, values: torch.Tensor, exit_ratio: float, model_name: str = "mpt_dolly_3b"):
-        """The ``values is not None`` branch of ``set_threshold`` (value_net.py:185-264)."""
+    def set_threshold_from_values(self, values: torch.Tensor, exit_ratio: float, model_name: str = "mpt_dolly_3b", engine=None):
+        """The ``values is not None`` branch of ``set_threshold`` (value_net.py:185-264).  engine: a ``DeerEngine``; with it and values on
+        the device the solver runs there (``DeerEngine.solve_thresholds``) and only the thresholds come back."""
+        if engine is not None and values.is_cuda:
+            counts = exit_counts(values.shape[1], self.real_num_exit, exit_ratio, self.exit_dist, model_name)
+            self._set_threshold_value(_solve_points(values, [counts], self.leq, engine)[0][0])
+            return values
         T = solve_thresholds(values[: self.real_num_exit], self.real_num_exit, exit_ratio, self.exit_dist, self.leq, model_name)
         self.thresholds = {self.exit_id_list[i]: float(T[i]) for i in range(self.real_num_exit)}
         self._version += 1
@@ -199,11 +253,14 @@ class ExitController:
 
 def controllers_from_values(value_net: Optional[ActionValueNet], exit_id_list: Sequence[int], values: torch.Tensor,
                             exit_ratios: Sequence[float], max_layers=None, steps_per_stage: int = 1, exit_dist: str = "exp",
-                            leq: bool = True, model_name: str = "mpt_dolly_3b") -> List[ExitController]:
+                            leq: bool = True, model_name: str = "mpt_dolly_3b", engine=None) -> List[ExitController]:
     """k operating points from ONE calibration: the ``values=`` branch of ``set_threshold`` (value_net.py:185-264) solved once per point
     on the same (n_exit, n_sample) value matrix.  max_layers: None (every exit reachable), one int for all points, or one per exit ratio
     (the reference's ``--max_layer``: DeeR-S vs DeeR-B).  Returns one ExitController per point, in order - a list that
-    ``MPTFlamingo.step_env_batch`` / ``evaluate_policy_batched(operating_points=...)`` take."""
+    ``MPTFlamingo.step_env_batch`` / ``evaluate_policy_batched(operating_points=...)`` take.
+    engine: a ``DeerEngine``; with it and values on the device (``generate_action_values(fused=True)``) the matrix stays there: the
+    points that share a number of reachable exits are solved in one ``DeerEngine.solve_thresholds`` call and one read of k x n_exit
+    thresholds (points with different max_layer: one call per group)."""
     ratios = [float(r) for r in exit_ratios]
     if max_layers is None or isinstance(max_layers, int):
         caps = [max_layers if max_layers is not None else list(exit_id_list)[-1] + 1] * len(ratios)
@@ -214,9 +271,71 @@ def controllers_from_values(value_net: Optional[ActionValueNet], exit_id_list: S
     out = []
     for r, cap in zip(ratios, caps):
         c = ExitController(value_net, exit_id_list, steps_per_stage=steps_per_stage, exit_dist=exit_dist, leq=leq, max_layer=cap)
-        c.set_threshold_from_values(values, r, model_name)
+        if engine is None or not values.is_cuda:
+            c.set_threshold_from_values(values, r, model_name)
         out.append(c)
+    if engine is not None and values.is_cuda:
+        for n_exit in sorted({c.real_num_exit for c in out}):
+            group = [i for i, c in enumerate(out) if c.real_num_exit == n_exit]
+            counts = [exit_counts(values.shape[1], n_exit, ratios[i], exit_dist, model_name) for i in group]
+            for i, row in zip(group, _solve_points(values, counts, leq, engine)[0]):
+                out[i]._set_threshold_value(row)
     return out
+
+
+def budget_ratio_grid(exit_dist: str, real_num_exit: int, grid: int, lo: Optional[float] = None, hi: Optional[float] = None) -> List[float]:
+    """``grid`` exit ratios over [lo, hi], by default the range in which the distribution still changes: 'exp' (probs ~ r**k) geometric
+    over [1/64, 64] - beyond, more than 98 % of the mass sits on the first / last exit; 'gauss' (mean exit index r, unit variance) linear
+    over [-3, n_exit + 2]; 'gamma' (shape r, scale 2, at 1 .. n_exit) linear over [0.05, n_exit + 2] - from nearly its most front-loaded
+    member (shape -> 0) to a mean 2 r well past the last exit."""
+    if exit_dist not in ("exp", "gauss", "gamma"):
+        raise ValueError("Unsupported exit distribution")
+    d_lo, d_hi = {"exp": (1.0 / 64, 64.0), "gauss": (-3.0, real_num_exit + 2.0), "gamma": (0.05, real_num_exit + 2.0)}[exit_dist]
+    lo, hi = float(d_lo if lo is None else lo), float(d_hi if hi is None else hi)
+    if grid < 2 or lo == hi:
+        return [lo]
+    if exit_dist == "exp":
+        return [lo * (hi / lo) ** (i / (grid - 1)) for i in range(grid)]
+    return [lo + (hi - lo) * i / (grid - 1) for i in range(grid)]
+
+
+def solve_for_budget(values: torch.Tensor, exit_id_list: Sequence[int], avg_exit_layer: float, max_layer: Optional[int] = None,
+                     exit_dist: str = "exp", leq: bool = True, model_name: str = "mpt_dolly_3b", engine=None, grid: int = 64,
+                     rounds: int = 2, value_net: Optional[ActionValueNet] = None, steps_per_stage: int = 1, trace: Optional[list] = None):
+    """The operating point for a BUDGET instead of a guessed exit ratio: the exit ratio whose predicted average exit layer
+    (``predicted_exit_mix``: layers per step on the calibration set, i.e. average LLM FLOPs) is the largest one not above
+    ``avg_exit_layer``.  Round 1 solves a grid of ``grid`` ratios over the distribution's range (``budget_ratio_grid``) on the one value
+    matrix and keeps the best point; every further round solves a grid between that point's two neighbours and keeps the better of the
+    two (ties: the earlier one, then the smaller ratio).  With an engine and values on the device every round is one
+    ``DeerEngine.solve_thresholds`` call and one small read - two of each for the default rounds = 2; engine=None runs the same search on
+    the host solver, point by point.  The prediction is that of the calibration samples, see ``predicted_exit_mix``.
+    Returns (ExitController with its thresholds set, the chosen exit ratio, (fractions, average_exit_layer)).  Raises ValueError naming
+    the reachable range when even the smallest average of round 1 lies above the budget.  trace: a list that receives one
+    (ratios, averages) pair per round."""
+    cap = max_layer if max_layer is not None else list(exit_id_list)[-1] + 1
+    ctl = ExitController(value_net, exit_id_list, steps_per_stage=steps_per_stage, exit_dist=exit_dist, leq=leq, max_layer=cap)
+    n_exit, n_sample = ctl.real_num_exit, values.shape[1]
+    ratios = budget_ratio_grid(exit_dist, n_exit, grid)
+    best = None                                      # (average, ratio, thresholds, exit counts)
+    for rnd in range(max(1, rounds)):
+        counts = [exit_counts(n_sample, n_exit, r, exit_dist, model_name) for r in ratios]
+        T, left = _solve_points(values, counts, leq, engine)
+        avgs = [predicted_exit_mix(n, ctl.exit_id_list)[1] for n in left]
+        if trace is not None:
+            trace.append((list(ratios), avgs))
+        ok = [i for i in range(len(ratios)) if avgs[i] <= avg_exit_layer]
+        if rnd == 0 and not ok:
+            raise ValueError(f"avg_exit_layer = {avg_exit_layer} is not reachable: '{exit_dist}' exit ratios {ratios[0]:.4g} .. {ratios[-1]:.4g} "
+                             f"predict average exit layers {min(avgs):.4g} .. {max(avgs):.4g} on this calibration set")
+        i = max(ok, key=lambda j: (avgs[j], -ratios[j])) if ok else None
+        if i is not None and (best is None or avgs[i] > best[0]):
+            best = (avgs[i], ratios[i], T[i], left[i])
+            lo, hi = ratios[max(i - 1, 0)], ratios[min(i + 1, len(ratios) - 1)]
+        elif rnd > 0:
+            break                                    # nothing better between the neighbours: the same interval again would repeat this grid
+        ratios = budget_ratio_grid(exit_dist, n_exit, grid, lo, hi)
+    ctl._set_threshold_value(best[2])
+    return ctl, best[1], predicted_exit_mix(best[3], ctl.exit_id_list)
 
 
 def generate_action_values(args, model, value_net: ActionValueNet, calvin_loader, device_id=None, generator=None, fused=False):

@@ -452,7 +452,19 @@ int deer_window_gather_layers(const float* P, const int* sel, const int* slot_of
                               int d, void* stream);
 int deer_exit_losses(const float* actions, const float* pose, const float* grip01, int Hn, long R, int A, float w_bin, float* num, float* bin,
                      float* loss, void* stream);
-/* ExitController.set_timestep (eval_utils.py:662-663) + per-step reset.  step_info: device int32[4] = {hold, step sequence
+/* ---- exit thresholds of many operating points from one calibration matrix (csrc/thresholds.hip): the solver of
+ * ExitController.set_threshold, value_net.py:242-262 ----
+ * values [n_stage][ld] f32 (n_sample deltas per row); out_n: DEVICE int32 [n_points][n_exit], the counts floor(n_sample * probs[e]) of
+ * every point, computed on the host in the reference's f32 arithmetic (deer_vla_amd.value_net.exit_counts).  For point p every sample
+ * starts alive; for e = 0 .. n_exit - 2, with c = out_n[p][e] and a alive samples: thresholds[p][e] = the c-th order statistic of
+ * values[e] over the alive samples (ascending for leq, descending otherwise) when 1 <= c <= a, else the sentinel -1e8 (leq) / +1e8; then
+ * every alive sample with v <= T (>= T) leaves and exit_counts[p][e] is their number.  The last exit gets +1e8 (-1e8) and the samples
+ * still alive.  status[p] = NaNs met in rows 0 .. n_exit - 2 (non-zero: do not trust point p).  One workgroup per point, radix select
+ * (four 8-bit passes) per exit; integer counting only, so the result is deterministic.  alive_scratch: n_points * n_sample bytes.
+ * n_exit <= 16, n_exit <= n_stage, ld >= n_sample. */
+int deer_solve_thresholds(const float* values, int n_stage, int n_sample, int ld, const int* out_n, int n_points, int n_exit, int leq,
+                          unsigned char* alive_scratch, float* thresholds, int* exit_counts, int* status, void* stream);
+/* ExitController.set_timestep (eval_utils.py:662-663) + per-step reset. step_info: device int32[4] = {hold, step sequence
  * number, host mirror pointer lo, hi} or NULL (no stage hold, no mirror). */
 int deer_ctl_begin_step(int* ctl, const int* step_info, int B, void* stream);
 

@@ -4,8 +4,12 @@ the thresholds of every (exit_ratio, max_layer) pair from that one value matrix,
 synthetic environments and prints one JSON line per point (ratio, cap, thresholds, avg_len, avg exit).  --compare also runs every point
 alone and prints the wall time of the sweep against the sum of the single-point runs.
 
-usage: sweep_operating_points.py --exit_ratio 0.6 0.8 1.0 1.2 [--max_layer 12 6] [--num_seq 16] [--n_envs 8] [--config tiny|3b]
-                                 [--ep_len 8] [--compare] [--fused-calibration]"""
+--avg-exit-layer X (repeatable) names the points by BUDGET instead: for every X (and cap) value_net.solve_for_budget finds the exit ratio whose
+predicted average exit layer on the calibration set is the largest one not above X - on the device when the calibration left its values there
+(--fused-calibration).
+
+usage: sweep_operating_points.py (--exit_ratio 0.6 0.8 1.0 1.2 | --avg-exit-layer 3 --avg-exit-layer 4.5) [--max_layer 12 6] [--num_seq 16]
+                                 [--n_envs 8] [--config tiny|3b] [--ep_len 8] [--compare] [--fused-calibration]"""
 import argparse
 import json
 import os
@@ -20,7 +24,7 @@ from deer_vla_amd import rollout as ro  # noqa: E402
 from deer_vla_amd import synthetic as syn  # noqa: E402
 from deer_vla_amd.config import deer_3b, deer_tiny  # noqa: E402
 from deer_vla_amd.factory import create_model_and_transforms  # noqa: E402
-from deer_vla_amd.value_net import ActionValueNet, controllers_from_values, generate_action_values  # noqa: E402
+from deer_vla_amd.value_net import ActionValueNet, controllers_from_values, generate_action_values, solve_for_budget  # noqa: E402
 
 TASKS = ["open", "push", "turn", "lift", "move"]      # one-word instructions (the idle slots' "idle" has the same length)
 
@@ -40,7 +44,10 @@ def calibration_loader(cfg, proc, tok, n_windows: int, W: int):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("--exit_ratio", type=float, nargs="+", required=True)
+    ap.add_argument("--exit_ratio", type=float, nargs="+", default=None)
+    ap.add_argument("--avg-exit-layer", type=float, action="append", default=None, metavar="X",
+                    help="an operating point by budget (repeatable): the exit ratio is solved so that the calibration set predicts an average "
+                         "exit layer of at most X (value_net.solve_for_budget); replaces --exit_ratio")
     ap.add_argument("--max_layer", type=int, nargs="*", default=None, help="DeeR-S / DeeR-B caps (the reference's --max_layer); default: every exit")
     ap.add_argument("--num_seq", type=int, default=16)
     ap.add_argument("--n_envs", type=int, default=8)
@@ -52,6 +59,8 @@ def main():
     ap.add_argument("--fused-calibration", action="store_true",
                     help="calibrate through window_exit_features + calibrate_values (one device pass per batch) instead of the per-step loop")
     args = ap.parse_args()
+    if (args.exit_ratio is None) == (args.avg_exit_layer is None):
+        ap.error("give the operating points either as --exit_ratio ... or as --avg-exit-layer X [--avg-exit-layer Y ...]")
 
     cfg = deer_tiny() if args.config == "tiny" else deer_3b()
     sd = syn.make_synthetic_state(cfg, 0, bf16_round=True) if args.config == "tiny" else syn.make_synthetic_state(cfg, seed=0, std="0.02", bf16_round=True)
@@ -64,8 +73,18 @@ def main():
                                        generator=torch.Generator().manual_seed(0), fused=args.fused_calibration)
     t_cal = time.perf_counter() - t0
     caps = args.max_layer or [exit_ids[-1] + 1]
-    pairs = [(r, m) for m in caps for r in args.exit_ratio]
-    points = controllers_from_values(vn, exit_ids, values, [r for r, _ in pairs], [m for _, m in pairs])
+    predicted = {}
+    if args.avg_exit_layer is not None:
+        pairs, points = [], []
+        for m in caps:
+            for budget in args.avg_exit_layer:
+                c, r, (_, avg) = solve_for_budget(values, exit_ids, budget, max_layer=m, engine=model.engine, value_net=vn)
+                pairs.append((r, m))
+                points.append(c)
+                predicted[len(points) - 1] = {"avg_exit_layer_budget": budget, "avg_exit_layer_predicted": avg}
+    else:
+        pairs = [(r, m) for m in caps for r in args.exit_ratio]
+        points = controllers_from_values(vn, exit_ids, values, [r for r, _ in pairs], [m for _, m in pairs], engine=model.engine)
 
     rng = np.random.default_rng(0)
     seqs = [(None, [TASKS[int(i)] for i in rng.integers(0, len(TASKS), 5)]) for _ in range(args.num_seq)]
@@ -78,9 +97,9 @@ def main():
     t0 = time.perf_counter()
     outs = ro.evaluate_policy_batched(w, envs, seqs, ann, ok, ep_len=args.ep_len, operating_points=points)
     t_sweep = time.perf_counter() - t0
-    for (r, m), c, o in zip(pairs, points, outs):
+    for p, ((r, m), c, o) in enumerate(zip(pairs, points, outs)):
         print(json.dumps({"exit_ratio": r, "max_layer": m, "thresholds": c.threshold_list(), "avg_len": o["avg_seq_len"],
-                          "avg_exit": o["avg_exit"], "n_steps": o["n_steps_all"], "exit_hist": o["exit_hist"]}))
+                          "avg_exit": o["avg_exit"], "n_steps": o["n_steps_all"], "exit_hist": o["exit_hist"], **predicted.get(p, {})}))
     summary = {"points": len(points), "n_envs": args.n_envs, "num_seq": args.num_seq, "calibration_s": round(t_cal, 3),
                "sweep_wall_s": round(t_sweep, 3)}
     if args.compare:
