@@ -199,7 +199,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(const float* __restrict__
   }
 }
 
-// The same for key sequences beyond PA_MAXKV (pre fusion at full size, flamingo_mpt.py:585-607: 2 x 256 patch tokens + 64 latents = 576
+// The same for key sequences beyond PA_MAXKV, up to 664 keys (the 156 KB of LDS the wrapper asks for) (pre fusion at full size, flamingo_mpt.py:585-607: 2 x 256 patch tokens + 64 latents = 576
 // keys): K and V pass through LDS in chunks of PAL_CH keys, the raw scores of all keys wait in `ps`, the softmax runs once over the row.
 #define PAL_CH 256
 #define PAL_MAXKV 1024
@@ -298,29 +298,33 @@ extern "C" int deer_attn_f32(const float* Q, const float* K1, const float* V1, c
   if (Q == nullptr || K1 == nullptr || V1 == nullptr || O == nullptr || batch <= 0 || heads <= 0 || q_len <= 0 || kv1 <= 0 || kv2 < 0 ||
       kv1 + kv2 > PAL_MAXKV || (kv2 > 0 && (K2 == nullptr || V2 == nullptr)) || (ldq & 3) || (ld1 & 3) || (ld2 & 3))
     return DEER_ERR_SHAPE;
+  // a row holds every head (the second segment's only when there is one: the ViT passes ld2 = 0 with kv2 = 0); float4 loads at every batch
+  if (ldo < heads * 64 || ldq < heads * 64 || ld1 < heads * 64 || (kv2 > 0 && ld2 < heads * 64) || (q_bstride & 3) || (bstride1 & 3) ||
+      (kv2 > 0 && (bstride2 & 3)))
+    return DEER_ERR_SHAPE;
   const int kv = kv1 + kv2;
   if (kv > PA_MAXKV) {                                    // long key sequences: chunked K / V
     const int smem_l = (PAL_CH * 65 + PA_QB * 64 + PA_QB * kv) * (int)sizeof(float);
+    if (smem_l > 156 * 1024) return DEER_ERR_SHAPE;          // kv <= 664
     static std::atomic<bool> attr_l{false};
     if (!attr_l) {
       if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_long_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess)
         return DEER_ERR_LAUNCH;
       attr_l = true;
     }
-    if (smem_l > 156 * 1024) return DEER_ERR_SHAPE;
     hipLaunchKernelGGL(attn_f32_long_kernel, dim3((q_len + PA_QB - 1) / PA_QB, heads, batch), dim3(256), smem_l, reinterpret_cast<hipStream_t>(stream), Q,
                        K1, V1, K2, V2, O, q_len, kv1, kv2, ldq, ld1, ld2, ldo, q_bstride, bstride1, bstride2, o_bstride, scale);
     DEER_LAUNCH_CHECK();
     return DEER_OK;
   }
   const int smem = (kv * 65 + PA_QB * 64 + PA_QB * kv) * (int)sizeof(float);
+  if (smem > 150 * 1024) return DEER_ERR_SHAPE;
   static std::atomic<bool> attr_set{false};
   if (!attr_set) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_f32_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess)
       return DEER_ERR_LAUNCH;
     attr_set = true;
   }
-  if (smem > 150 * 1024) return DEER_ERR_SHAPE;
   hipLaunchKernelGGL(attn_f32_kernel, dim3((q_len + PA_QB - 1) / PA_QB, heads, batch), dim3(256), smem, reinterpret_cast<hipStream_t>(stream), Q,
                      K1, V1, K2, V2, O, q_len, kv1, kv2, ldq, ld1, ld2, ldo, q_bstride, bstride1, bstride2, o_bstride, scale);
   DEER_LAUNCH_CHECK();
@@ -398,6 +402,10 @@ extern "C" int deer_xattn_f32(const float* qslab, int s_in, long slab_stride, in
                               const int* text_time, int n_per_media, float* out, int ldo, int T, int n_kv, int heads, int batch, float scale,
                               const int* ctl, void* stream) {
   if (T <= 0 || T > PX_MAXT || n_kv <= 0 || n_kv > PX_MAXKV || s_in <= 0 || n_per_media <= 0 || batch <= 0 || (ldkv & 3) || (ldqs & 3))
+    return DEER_ERR_SHAPE;
+  // k of head h at column h*64, v at column inner + h*64 of a kv row; float4 loads of every slab
+  if (qslab == nullptr || kv == nullptr || text_time == nullptr || out == nullptr || heads <= 0 || inner < heads * 64 || (inner & 3) ||
+      ldo < heads * 64 || ldqs < heads * 64 || ldkv < inner + heads * 64 || (s_in > 1 && (slab_stride & 3)))
     return DEER_ERR_SHAPE;
   const int smem = (PX_MAXT * 65 + PX_MAXT * (PX_MAXKV + 1) + PX_MAXKV * 65 + PX_MAXKV * 64) * (int)sizeof(float);
   static std::atomic<bool> attr_set{false};

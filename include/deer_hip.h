@@ -286,7 +286,7 @@ int deer_gemm_f32_nt(const float* A, int lda, const float* W, int ldw, const flo
                      int epi, void* stream);
 /* open_clip MHA core / PerceiverAttention core (helpers.py:47-73) in fp32: q [batch][q_len][ldq] (head h at column h*64), keys and
  * values in one or two segments ([batch][kv_s][ld_s], pointers at the K / V column offset), out f32 [batch][q_len][ldo].
- * head_dim 64, kv1 + kv2 <= 352 with the keys of a head resident in LDS; up to ~700 keys (pre fusion: 576) through a chunked form. */
+ * head_dim 64, kv1 + kv2 <= 352 with the keys of a head resident in LDS; up to 664 keys (pre fusion: 576) through a chunked form (its 156 KB of LDS). */
 int deer_attn_f32(const float* Q, const float* K1, const float* V1, const float* K2, const float* V2, float* O, int batch, int heads,
                   int q_len, int kv1, int kv2, int ldq, int ld1, int ld2, int ldo, long q_bstride, long bstride1, long bstride2,
                   long o_bstride, float scale, void* stream);
