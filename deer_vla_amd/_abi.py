@@ -166,6 +166,8 @@ SIGNATURES = {
     "deer_exit_n_heads": [P],
     # exit thresholds of many operating points in one launch (csrc/thresholds.hip)
     "deer_solve_thresholds": [P, I, I, I, P, I, I, I, P, P, P, P, P],
+    # on-policy exit values: the deltas of a shadow step appended to a device value matrix (csrc/value_log.hip)
+    "deer_value_log_append": [P, I, I, I, P, I, I, P, P, P],
     "deer_model_scratch_bytes": [P],
     "deer_model_n_chains": [P],
     "deer_prof_enable": [P, I],

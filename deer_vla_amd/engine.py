@@ -340,6 +340,13 @@ class DeerEngine:
 
     def configure_exit(self, exit_ids: Sequence[int], max_layer: int, steps_per_stage: int = 1):
         """``ExitController.__init__`` (value_net.py:164-173): max_layer = min(max_layer-1, last exit)."""
+        vlog = getattr(self, "_vlog", None)
+        if vlog is not None:                                      # an open value log has one row per exit of the time it was opened
+            ids = list(exit_ids)
+            n_new = len([x for x in ids if x <= min(max_layer - 1, ids[-1])])
+            if n_new != vlog[0].shape[0]:
+                raise RuntimeError(f"a value log for {vlog[0].shape[0]} exits is open: configure_exit to {n_new} reachable exits needs "
+                                   "close_value_log() first")
         old = (self.exit_ids, self._max_layer_arg)
         self.exit_ids = list(exit_ids)
         self._max_layer_arg = max_layer
@@ -468,6 +475,7 @@ class DeerEngine:
         self._head_state_changed()
         self.ctl.zero_()
         self._shadow_on = False
+        self._last_step_shadow = False                              # the control blocks no longer hold a shadow step's deltas
         self.cur_step = 0
         self._window_hidden = None                                  # DeterministicDecoder: h_n of a window call over another batch size
 
@@ -663,6 +671,7 @@ class DeerEngine:
         # but only while that step's ALL_EXITED is still set): nothing of this step may start before they are gone
         self._drain_side_streams()
         T, use_mask = self.load_inputs(rgb, gripper, ids, mask)
+        self._last_step_shadow = bool(shadow)
         if bool(shadow) != getattr(self, "_shadow_on", False):
             self.ctl[abi.CTL_SHADOW] = 1 if shadow else 0
             self._shadow_on = bool(shadow)
@@ -1012,6 +1021,62 @@ class DeerEngine:
         from .ops import run_solve_thresholds
         T, left, status = run_solve_thresholds(self.lib, values.to(device=self.dev), counts, leq)
         return (T, left, status) if return_status else (T, left)
+
+    # ------------------------------------------------------------------------------ on-policy exit values (csrc/value_log.hip)
+    def open_value_log(self, capacity: int):
+        """A device-resident log of on-policy exit values: values (real_num_exit, capacity) f32 - the matrix ``solve_thresholds`` takes -
+        taken (capacity,) i32 and the three state words {count, dropped, nonfinite}.  ``log_values`` appends to it after a shadow step.
+        Sized for the ``real_num_exit`` of now: ``configure_exit`` to another count raises while it is open."""
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError(f"open_value_log: capacity must be positive, got {capacity}")
+        if getattr(self, "_vlog", None) is not None:
+            raise RuntimeError("a value log is already open (close_value_log() first)")
+        with torch.cuda.device(self.dev):
+            self._vlog = (torch.zeros(self.real_num_exit, capacity, dtype=torch.float32, device=self.dev),
+                          torch.zeros(capacity, dtype=torch.int32, device=self.dev), torch.zeros(3, dtype=torch.int32, device=self.dev))
+
+    def log_values(self, active=None):
+        """Append the deltas of the last step - which must have been a SHADOW step - and the exit layer every environment took to the open
+        value log: one column per environment of ``active`` (None: all; an iterable of environment indices; or an int mask, bit b =
+        environment b), in ascending environment order.  One launch on the current stream behind the step (deer_value_log_append): no
+        host synchronisation, outside the step's graph, nothing recaptured.  Columns beyond the capacity are counted as dropped."""
+        from .ops import run_value_log_append
+        vlog = getattr(self, "_vlog", None)
+        if vlog is None:
+            raise RuntimeError("log_values: no value log is open (open_value_log(capacity))")
+        if not getattr(self, "_last_step_shadow", False):
+            raise RuntimeError("log_values: the last step was not a shadow step (step(..., shadow=True)): its control blocks hold the deltas "
+                               "of the exits it evaluated before it stopped, not of every exit")
+        if active is None:
+            mask = (1 << self.B) - 1
+        elif isinstance(active, int):
+            mask = active
+        else:
+            mask = 0
+            for b in active:
+                if not 0 <= int(b) < self.B:
+                    raise ValueError(f"log_values: environment {b} of an env batch of {self.B}")
+                mask |= 1 << int(b)
+        if mask < 0 or mask >> self.B:
+            raise ValueError(f"log_values: mask {mask:#x} names environments beyond the {self.B} of the batch")
+        values, taken, state = vlog
+        run_value_log_append(self.lib, self.ctl, self.B, values.shape[0], mask, values, values.shape[1], taken, state)
+
+    def logged_values(self):
+        """(values[:, :count], taken[:count], dropped, nonfinite) of the open value log: device VIEWS of the log (later appends go behind
+        them) after ONE small read of the three state words, which waits for the appends enqueued so far.  taken holds exit LAYERS
+        (``exit_ids`` members); dropped: columns that found no room; nonfinite: non-finite deltas among the logged ones."""
+        vlog = getattr(self, "_vlog", None)
+        if vlog is None:
+            raise RuntimeError("logged_values: no value log is open (open_value_log(capacity))")
+        values, taken, state = vlog
+        count, dropped, nonfinite = (int(v) for v in state.cpu())
+        return values[:, :count], taken[:count], dropped, nonfinite
+
+    def close_value_log(self):
+        """Frees the value log (views handed out by ``logged_values`` keep their storage alive)."""
+        self._vlog = None
 
     def window_exit_pooled(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8, hidden: bool = False):
         """The grouped static full-depth window pass of ``window_hidden_states`` reduced to what the all-exits forward reads: the POOLED

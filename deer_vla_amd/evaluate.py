@@ -9,6 +9,9 @@ One batch is what the reference's CALVIN loader yields, by name:
   state             (bs, W, 15) robot_obs rows (use_state models only)
 The frames go through ``MPTFlamingo.all_exit_actions`` (one static full-depth pass + ``DeerEngine.exit_outputs``), the losses through
 ``DeerEngine.exit_losses``; the per-head sums stay on the device until the end.
+
+``on_policy_values`` is the other evaluation without labels: the exit values of a live rollout (shadow steps logged on the device), the
+input of ``value_net.calibrate_on_policy``.
 """
 from __future__ import annotations
 
@@ -85,3 +88,42 @@ def exit_losses_on_windows(model, batches: Iterable[Dict[str, torch.Tensor]], w_
     names = [f"exit{k}" for k in range(n_layer_heads)] + ["final", "extra", "extra2"]
     return {"heads": names, "num": means[0].tolist(), "bin": means[1].tolist(), "loss": means[2].tolist(),
             "total": float((means[2] * w).sum()), "rows": count, "w_bin": float(w_bin)}
+
+
+def on_policy_values(wrapper, envs, eval_sequences, annotations, task_checker, controller, n_samples: int, ep_len: Optional[int] = None):
+    """Exit values ON POLICY: the batched rollout loop (``rollout.evaluate_policy_batched``) on ``envs`` under ``controller``'s
+    thresholds, every step a SHADOW step - all exits evaluated, every environment's LSTM history committed at the exit its criterion
+    takes, as in a normal rollout - whose deltas and exit layers are appended to a value log on the device (``DeerEngine.log_values``,
+    csrc/value_log.hip) until ``n_samples`` columns are there; the chains are run again from the start while the log is short.  The
+    host reads three words per pass over the chains and the (n_samples,) exit layers at the end; the matrix never leaves the device.
+    Returns (values (real_num_exit, n_samples) f32 on the device - what ``DeerEngine.solve_thresholds`` / ``solve_for_budget(engine=...)``
+    take, taken (n_samples,) i32 exit layers on the device, (fractions, average exit layer) measured from taken -
+    ``value_net.measured_exit_mix``).  This rank's chains only.  wrapper: a ``rollout.BatchedModelWrapper``; controller: a native
+    ``ExitController`` with its thresholds set and ``steps_per_stage`` = 1 (a held step evaluates no exit: its deltas are NaN, which
+    raises ValueError here like any other non-finite delta)."""
+    from .rollout import EP_LEN, evaluate_policy_batched
+    from .value_net import measured_exit_mix
+    n_samples = int(n_samples)
+    if n_samples < 1:
+        raise ValueError(f"on_policy_values: n_samples must be positive, got {n_samples}")
+    ctl = getattr(controller, "module", controller)
+    m = wrapper.model.module
+    e = m.engine
+    m._sync_controller(ctl)                                  # the log is sized for this controller's reachable exits
+    prev_ctl, wrapper.exit_controller = wrapper.exit_controller, ctl
+    e.open_value_log(n_samples)
+    try:
+        count = 0
+        while count < n_samples:
+            evaluate_policy_batched(wrapper, envs, eval_sequences, annotations, task_checker, ep_len=EP_LEN if ep_len is None else ep_len,
+                                    log_values=n_samples - count)
+            values, taken, _, nonfinite = e.logged_values()
+            if values.shape[1] == count:
+                raise ValueError("on_policy_values: a pass over the evaluation chains logged no step")
+            count = values.shape[1]
+        if nonfinite:
+            raise ValueError(f"on_policy_values: {nonfinite} non-finite deltas among the logged exit values")
+    finally:
+        e.close_value_log()
+        wrapper.exit_controller = prev_ctl
+    return values, taken, measured_exit_mix(taken, ctl.exit_id_list[: ctl.real_num_exit])

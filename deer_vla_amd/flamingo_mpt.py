@@ -323,7 +323,10 @@ class MPTFlamingo(nn.Module):
         if e.env_caps is not None:                                        # per-environment controllers were in use
             e.clear_env_exit()
             self._ctl_sig = None
-        sig = (tuple(ctl.exit_id_list), ctl.max_layer, ctl.steps_per_stage, ctl._version, ctl.leq)
+        # the thresholds themselves are part of the signature: two controllers at the same version (a re-solved one replacing the one it
+        # was solved from, value_net.calibrate_on_policy) differ in nothing else
+        sig = (tuple(ctl.exit_id_list), ctl.max_layer, ctl.steps_per_stage, ctl._version, ctl.leq,
+               tuple(ctl.thresholds.values()) if ctl.thresholds is not None else None)
         if sig != self._ctl_sig:
             e.configure_exit(ctl.exit_id_list, ctl.max_layer + 1, ctl.steps_per_stage)
             assert e.ctl_max_layer == ctl.max_layer
@@ -404,14 +407,16 @@ class MPTFlamingo(nn.Module):
         return CausalLMOutputWithPast(logits=[1.0], hidden_states=hidden, exit_layer=b)
 
     def step_env_batch(self, vision_x, lang_x, attention_mask, vision_gripper, exit_controller=None, exit_id=None, ensemble=False,
-                       env_steps=None):
+                       env_steps=None, shadow=False):
         """One control step of ALL n_envs environments (north_star: one env batch per rank): vision_x / vision_gripper
         (n_envs, ..., 3, S, S), lang_x / attention_mask (n_envs, T) right-padded.  Returns (pose (n_envs, 6), gripper prob (n_envs,),
         exit layers list); ``ensemble``: the mean of every environment's last two exit-check actions instead (eval_utils.py:457-461).  Every environment exits at its own layer on the device; LSTM state per environment.
         ``env_steps``: every environment's step index inside its own sub-task - the per-rollout ``set_timestep(step)`` of the reference
         (eval_utils.py:662-663) for a controller with ``steps_per_stage`` > 1 (value_net.py:285-286); default: the controller's cur_step.
         ``exit_controller`` may also be a list of n_envs native controllers, one per environment (sharing exit_id_list, threshold type and
-        leq; own thresholds, max_layer and steps_per_stage): one batch then carries several operating points."""
+        leq; own thresholds, max_layer and steps_per_stage): one batch then carries several operating points.
+        ``shadow``: ``DeerEngine.step(shadow=True)`` - every exit is evaluated and its delta recorded, every environment commits at the
+        first exit whose criterion fires (the exit layer returned) and the step never stops early: what ``DeerEngine.log_values`` logs."""
         e = self.engine
         if isinstance(exit_controller, (list, tuple)):                   # one controller per environment (operating-point sweeps)
             if exit_id is not None:
@@ -425,7 +430,7 @@ class MPTFlamingo(nn.Module):
             if exit_id is None:
                 assert isinstance(ctl, ExitController), "env batches take the native controller (device-side exit gate)"
                 self._sync_controller(ctl)
-        r = e.step(vision_x, vision_gripper, lang_x, attention_mask, exit_id=exit_id, env_steps=env_steps)
+        r = e.step(vision_x, vision_gripper, lang_x, attention_mask, exit_id=exit_id, env_steps=env_steps, shadow=shadow)
         r = r if isinstance(r, list) else [r]
         exits = [x["exit_layer"] for x in r]
         A = e.A
@@ -565,7 +570,7 @@ class MPTFlamingo(nn.Module):
                 use_cache: bool = False, vision_gripper=None, state_tensor=None, return_feature=False, policy_mask=None,
                 act=None, deterministic=False, with_gripper_logits=False, exit_id=None, dynamic_early_exit=False,
                 exit_controller=None, return_in_feat=False, return_aggregate_feature=False, only_extra_exit=False,
-                eval_time=False, no_backbone_grad=False):
+                eval_time=False, no_backbone_grad=False, shadow=False):
         assert (vision_x is not None) or use_cached_vision_x, "Must provide either vision_x or use_cached_vision_x to True."
         if use_cached_vision_x:
             raise NotImplementedError("use_cached_vision_x is not used on the DeeR robot path")
@@ -599,7 +604,9 @@ class MPTFlamingo(nn.Module):
         if exit_id is not None or native:
             if native and exit_id is None:
                 self._sync_controller(ctl)
-            r = e.step(vision_x, vision_gripper, lang_x, attention_mask, exit_id=exit_id, state=state_tensor if self.use_state else None)
+            # shadow (native dynamic exit only): every exit evaluated, committed at the first that fires - DeerEngine.log_values' input
+            r = e.step(vision_x, vision_gripper, lang_x, attention_mask, exit_id=exit_id, state=state_tensor if self.use_state else None,
+                       shadow=bool(shadow) and native and exit_id is None)
             exit_layer = r["exit_layer"]
             if native and exit_id is None:
                 ctl.cur_exit_id = int(e.ctl_host[abi.CTL_CUR_EXIT_ID])

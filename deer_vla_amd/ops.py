@@ -17,6 +17,10 @@ through PyTorch-ROCm custom ops").  These are the three coarse operators SURVEY.
                                                                                the solver of ExitController.set_threshold
                                                                                (value_net.py:242-262), k operating points per launch;
                                                                                model-free (no ``model`` argument)
+  deer::value_log_append(Tensor ctl, int n_envs, int n_exit, int active_mask, Tensor(a!) values, int capacity, Tensor(b!) taken,
+                         Tensor(c!) state) -> ()                               the deltas a shadow step left in the control blocks
+                                                                               (value_net.py:120-133), one column per environment of
+                                                                               active_mask, appended to a device value matrix; model-free
 
 ``model`` is the address of a ``deer_model`` (``NativeModel.handle``): weights, workspace, LSTM state and the exit controller
 configuration live in that object, like they live in the reference's stateful ``MPTFlamingo`` module.
@@ -464,6 +468,48 @@ def _(values, counts, leq):
     _, _, k, n_exit = solve_thresholds_shapes(values, counts)
     return (values.new_empty((k, n_exit), dtype=torch.float32), values.new_empty((k, n_exit), dtype=torch.int32),
             values.new_empty((k,), dtype=torch.int32))
+
+
+def value_log_shapes(ctl, n_envs: int, n_exit: int, active_mask: int, values, capacity: int, taken, state):
+    """Host-side checks of one append to a value log (no device touched): ctl int32 control blocks of n_envs environments, values
+    (n_exit or more rows, capacity or more columns) float32 with unit column stride, taken (capacity,) int32, state (3,) int32 =
+    {count, dropped, nonfinite}.  Returns the row stride of values."""
+    if ctl.dtype != torch.int32 or ctl.numel() < n_envs * abi.CTL_WORDS or not ctl.is_contiguous():
+        raise ValueError(f"value_log_append: ctl must hold {n_envs} contiguous int32 control blocks, got {tuple(ctl.shape)} {ctl.dtype}")
+    if not 1 <= n_envs <= abi.MAX_ENVS or not 1 <= n_exit <= 16:
+        raise ValueError(f"value_log_append: n_envs = {n_envs} (1..{abi.MAX_ENVS}), n_exit = {n_exit} (1..16)")
+    if active_mask < 0 or active_mask >> n_envs:
+        raise ValueError(f"value_log_append: active_mask {active_mask:#x} names environments beyond the {n_envs} of the batch")
+    if values.dim() != 2 or values.dtype != torch.float32 or values.shape[0] < n_exit or values.shape[1] < capacity or capacity < 1 \
+            or values.stride(1) != 1 or not capacity <= values.stride(0) <= 0x7fffffff:
+        raise ValueError(f"value_log_append: values must be ({n_exit}+, {capacity}+) float32 rows, got {tuple(values.shape)} {values.dtype} "
+                         f"strides {tuple(values.stride())}")
+    if taken.dtype != torch.int32 or taken.dim() != 1 or taken.numel() < capacity or not taken.is_contiguous():
+        raise ValueError(f"value_log_append: taken must be ({capacity},) int32, got {tuple(taken.shape)} {taken.dtype}")
+    if state.dtype != torch.int32 or state.numel() != 3 or not state.is_contiguous():
+        raise ValueError(f"value_log_append: state must be 3 int32 words, got {tuple(state.shape)} {state.dtype}")
+    return int(values.stride(0))
+
+
+def run_value_log_append(lib, ctl: torch.Tensor, n_envs: int, n_exit: int, active_mask: int, values: torch.Tensor, capacity: int,
+                         taken: torch.Tensor, state: torch.Tensor):
+    """One ``deer_value_log_append`` launch on the current stream (csrc/value_log.hip); nothing is synchronised or allocated."""
+    ld = value_log_shapes(ctl, n_envs, n_exit, active_mask, values, capacity, taken, state)
+    abi.check(lib.deer_value_log_append(abi.ptr(ctl), n_envs, n_exit, active_mask, abi.ptr(values), ld, capacity, abi.ptr(taken), abi.ptr(state),
+                                        _stream()), "deer_value_log_append")
+
+
+@torch.library.custom_op("deer::value_log_append", mutates_args=("values", "taken", "state"), device_types="cuda")
+def value_log_append(ctl: torch.Tensor, n_envs: int, n_exit: int, active_mask: int, values: torch.Tensor, capacity: int, taken: torch.Tensor,
+                     state: torch.Tensor) -> None:
+    """Appends the deltas (ctl[b][CTL_DELTAS + e], e < n_exit) and the exit layer of every environment of active_mask to the value log
+    (values, taken, state = {count, dropped, nonfinite}) after a shadow step: on-policy exit values (value_net.py:120-133)."""
+    run_value_log_append(abi.lib(), ctl, n_envs, n_exit, active_mask, values, capacity, taken, state)
+
+
+@value_log_append.register_fake
+def _(ctl, n_envs, n_exit, active_mask, values, capacity, taken, state):
+    value_log_shapes(ctl, n_envs, n_exit, active_mask, values, capacity, taken, state)
 
 
 def decode_ctl(ctl: torch.Tensor):

@@ -433,9 +433,11 @@ class BatchedModelWrapper:
             self._blank = torch.zeros_like(ref)
         return torch.stack([x if x is not None else self._blank for x in live])
 
-    def step(self, obs_list, goals, env_steps=None, exit_controller=None):
+    def step(self, obs_list, goals, env_steps=None, exit_controller=None, shadow=False, log=None):
         """env_steps: step index of every slot inside its sub-task (idle slots: 0); only read by a controller with steps_per_stage > 1.
-        exit_controller: overrides the wrapper's for this step (evaluate_policy_batched's sweep hands every slot's point here)."""
+        exit_controller: overrides the wrapper's for this step (evaluate_policy_batched's sweep hands every slot's point here).
+        shadow: a shadow step (MPTFlamingo.step_env_batch); log: also append the deltas and exit layers of the slots that stepped (those
+        with an observation) to the engine's open value log (DeerEngine.log_values) - on-policy exit values."""
         ctl = exit_controller if exit_controller is not None else self.exit_controller
         rgb = self._frames(obs_list, "rgb_static")
         grip = self._frames(obs_list, "rgb_gripper")
@@ -451,7 +453,9 @@ class BatchedModelWrapper:
             pose, g, exits = self.model.module.step_env_batch(rgb.to(self.cast_type).cuda(non_blocking=True), ids, mask,
                                                               grip.to(self.cast_type).cuda(non_blocking=True),
                                                               exit_controller=ctl, exit_id=self.exit_id,
-                                                              ensemble=self.use_action_ensemble, env_steps=env_steps)
+                                                              ensemble=self.use_action_ensemble, env_steps=env_steps, shadow=shadow)
+            if log:
+                self.model.module.engine.log_values([b for b, o in enumerate(obs_list) if o is not None])
         self.current_exit_layers = exits
         A = self.model.module.act_step
         if A != 1:                                                 # eval_utils.py:466-475 per slot: (B, A, 7), the harness executes the first of them
@@ -479,7 +483,8 @@ def _idle_controller(points):
 
 
 def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_sequences, annotations, task_checker, ep_len: int = EP_LEN,
-                            report: bool = False, groups: Sequence = (), operating_points: Optional[Sequence] = None):
+                            report: bool = False, groups: Sequence = (), operating_points: Optional[Sequence] = None,
+                            log_values: Optional[int] = None):
     """``evaluate_policy_ddp`` with one env batch per rank: this rank's chains (same slicing, eval_utils.py:523-527) are dealt
     to the n_envs slots, which run them concurrently - per slot exactly the reference's chain / sub-task / step loop
     (eval_utils.py:583-684), per step ONE engine call for all slots.  Metrics reduce like evaluate_policy_ddp.
@@ -494,7 +499,11 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
     bayesian_optimization.py) as ONE run: the jobs are (point, chain) pairs, every chain of this rank runs once per point, a slot
     that takes a job switches to that point's row and cap (device table, no graph recapture).  Returns a list of k metric dicts (rank
     0), each what a run with that controller alone reports (``wall_s_mean`` / ``steps_per_s``: the whole sweep's wall time); the
-    metrics of all points reduce in ONE all-reduce."""
+    metrics of all points reduce in ONE all-reduce.
+
+    ``log_values``: n - every step is a SHADOW step whose deltas and exit layers go to the engine's open value log
+    (``BatchedModelWrapper.step(shadow=True, log=True)``), and the run stops once n columns are logged; chains cut short count with the
+    sub-tasks they had solved (``evaluate.on_policy_values`` reads the log, not these metrics)."""
     import threading
     import torch.distributed as dist
     rank = dist.get_rank() if dist.is_available() and dist.is_initialized() else 0
@@ -511,6 +520,8 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
     ok_exits, fail_exits, ok_steps = [[] for _ in range(k)], [[] for _ in range(k)], [[] for _ in range(k)]
     lock = threading.Lock()
     n_steps_box = [0] * k
+    n_logged = [0]
+    log_kw = {} if log_values is None else {"shadow": True, "log": True}
     errors = []
     idle = _idle_controller(points) if points is not None else None
 
@@ -546,12 +557,21 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
         for b in range(B):
             next_chain(b)
         while any(s is not None for s in slot):
+            if log_values is not None and n_logged[0] >= log_values:
+                with lock:
+                    for st in slot:
+                        if st is not None:
+                            results[st["p"]].setdefault(st["seq_i"], st["n_ok"])
+                break
             if ctls is None and model.exit_controller is not None:  # eval_utils.py:662-663: every slot's own step index goes with the step
                 model.exit_controller.module.set_timestep(0)
             obs = [envs[b].get_obs() if slot[b] is not None else None for b in range(B)]
             acts = model.step(obs, [slot[b]["goal"] if slot[b] is not None else None for b in range(B)],
                               env_steps=[slot[b]["step"] if slot[b] is not None else 0 for b in range(B)],
-                              **({} if ctls is None else {"exit_controller": list(ctls)}))
+                              **({} if ctls is None else {"exit_controller": list(ctls)}), **log_kw)
+            if log_values is not None:
+                with lock:
+                    n_logged[0] += sum(s is not None for s in slot)
             for b in range(B):
                 st = slot[b]
                 if st is None:
@@ -608,7 +628,7 @@ def evaluate_policy_batched(model: BatchedModelWrapper, envs: Sequence, eval_seq
             raise errors[0]
     B = sum(mw.B for mw, _ in members)
     wall = time.perf_counter() - t0
-    res = [[results[p][i] for i in range(len(mine))] for p in range(k)]
+    res = [[results[p][i] for i in range(len(mine)) if log_values is None or i in results[p]] for p in range(k)]
     packed = torch.stack([torch.cat([ddist.pack_metrics(res[p], ok_exits[p], n_layer, wall),
                                      torch.tensor([float(n_steps_box[p])], dtype=torch.float64)]) for p in range(k)])
     outs = ddist.reduce_metrics_points(packed, n_extra=1)        # ONE all-reduce for every point

@@ -464,6 +464,16 @@ int deer_exit_losses(const float* actions, const float* pose, const float* grip0
  * n_exit <= 16, n_exit <= n_stage, ld >= n_sample. */
 int deer_solve_thresholds(const float* values, int n_stage, int n_sample, int ld, const int* out_n, int n_points, int n_exit, int leq,
                           unsigned char* alive_scratch, float* thresholds, int* exit_counts, int* status, void* stream);
+/* On-policy exit values (csrc/value_log.hip): after a SHADOW step (DEER_CTL_SHADOW: every exit evaluated, its delta of
+ * ActionValueNet.forward(mode='infer'), value_net.py:120-133, in ctl[b][DEER_CTL_DELTAS + e]) append one column per environment of
+ * active_mask (bit b = environment b, ascending b) to values [n_exit][ld] f32: column count + (active environments below b) receives the
+ * n_exit deltas of environment b bit for bit, taken[column] its DEER_CTL_EXIT_LAYER - the sample of the "average exit layer" that
+ * bayesian_optimization.py:75-79 takes as its budget.  state: device int32[3] = {count, dropped, nonfinite}: columns in use, columns that
+ * found no room (columns at or beyond capacity are not written), non-finite deltas written.  One workgroup, no atomics: appends are
+ * ordered by their stream.  Does not consult ALL_EXITED.  n_envs 1..DEER_MAX_ENVS, n_exit 1..16, capacity >= 1, ld >= capacity, no bit
+ * of active_mask at or above n_envs. */
+int deer_value_log_append(const int* ctl, int n_envs, int n_exit, int active_mask, float* values, int ld, int capacity, int* taken,
+                          int* state, void* stream);
 /* ExitController.set_timestep (eval_utils.py:662-663) + per-step reset. step_info: device int32[4] = {hold, step sequence
  * number, host mirror pointer lo, hi} or NULL (no stage hold, no mirror). */
 int deer_ctl_begin_step(int* ctl, const int* step_info, int B, void* stream);
