@@ -164,6 +164,19 @@ SIGNATURES = {
     "deer_pool_window_layers": [P, I, I, P, P],
     "deer_exit_outputs": [P, P, I, P, P, I, I, P, P],
     "deer_exit_n_heads": [P],
+    # exit-only fine-tuning of one head (csrc/head_grad.hip, include/deer_model.h deer_head_loss_grad)
+    "deer_head_grad_ln": [P, L, P, L, P, P, P, I, I, F, I, P],
+    "deer_head_grad_lstm_step": [P, L, P, L, P, P, P, P, L, P, L, I, I, P],
+    "deer_head_grad_loss": [P, P, P, L, I, F, F, P, P, P, P, P],
+    "deer_head_grad_gemm": [P, L, I, P, L, I, P, L, I, I, I, I, P],
+    "deer_head_grad_colsum": [P, L, P, L, P, P, P, P, I, I, I, P],
+    "deer_head_grad_relu_mask": [P, P, L, P],
+    "deer_head_grad_ln_bwd": [P, L, P, L, P, P, P, L, I, I, P],
+    "deer_head_grad_lstm_bwd_step": [P, L, P, P, P, L, P, P, P, L, P, I, I, P],
+    "deer_adamw_step": [P, P, P, P, L, P, P, I, P, I, P],
+    "deer_head_param_count": [P, I],
+    "deer_head_param_entry": [P, I, I, P, I, P, P, P],
+    "deer_head_loss_grad": [P, I, P, P, I, I, P, P, F, F, P, I, P, P],
     # exit thresholds of many operating points in one launch (csrc/thresholds.hip)
     "deer_solve_thresholds": [P, I, I, I, P, I, I, I, P, P, P, P, P],
     # on-policy exit values: the deltas of a shadow step appended to a device value matrix (csrc/value_log.hip)

@@ -127,6 +127,17 @@ struct HeadW {
   int layer = -1;                                   // exit layer the head serves (per-layer heads)
 };
 
+// exit-only fine-tuning (csrc/head_grad.hip): one head's parameters as a flat f32 buffer OUTSIDE the arena, in the reference's state-dict
+// order; the LstmW / FcW offsets below count floats from the start of that buffer
+struct HeadParam { std::string name; long offset, numel; int decays; };
+struct HeadFlat {
+  std::vector<HeadParam> e;
+  std::vector<LstmW> lstm;
+  std::vector<FcW> fc;
+  size_t wa, ba, wg, bg;
+  long total = 0;
+};
+
 // f32 activation buffers of the fp32-activation arithmetic (deer_config.precision = 1; batched single-stream schedule only)
 struct PreciseWS {
   size_t im2col, xn, qkv, ao, h, mln, mkv, latln, pqkv, pao, pln, ph, kv_all;
@@ -213,6 +224,9 @@ struct deer_model {
   size_t calib_bytes = 0;
   void* exit_scratch = nullptr;     // deer_exit_outputs: pooled / gathered feature rows of the all-exits pass, same rule
   size_t exit_bytes = 0;
+  std::vector<HeadFlat> hflat;      // deer_head_param_entry / deer_head_loss_grad: [0] extra_exit, [k] per-layer head k
+  void* grad_scratch = nullptr;     // deer_head_loss_grad: tape + gradient temporaries of one call, same rule
+  size_t grad_bytes = 0;
   bool head_pre = true;             // recurrent half of the LSTM head once per control step (DEER_HEAD_PRE=0: every evaluation streams W_hh again)
   bool ghh_valid = false;           // the pre-pass result matches h_state: set by deer_begin_step, cleared by deer_model_head_state_changed
   bool compact = true;              // env batches: compaction of exited environments (DEER_COMPACT=0 / deer_model_set_compaction)
@@ -472,6 +486,66 @@ void build_arena(deer_model* m) {
     HeadW& h = m->lw.back();
     h.layer = c.n_layers - 1;
     add_head("lm_head.", h.lstm, h.fc, h.wa, h.ba, h.wg, h.bg);
+  }
+}
+
+// ---- flat parameter tables of the heads (exit-only fine-tuning) ----------------------------------------------------------------------
+// The reference's state-dict order of one DeterministicDecoder (action_head.py:466-473: rnn, actions, gripper; add_head above registers the
+// same names for ingestion).  decays: the reference's apply_decay for a head tensor (train_calvin_post_strategy.py:471-482) - Linear and
+// LSTM weights; no bias, no LayerNorm tensor.
+void build_head_flat(deer_model* m) {
+  const deer_config& c = m->c;
+  const int d = m->d, H = m->H, A = std::max(1, c.multi_step_action);
+  std::vector<std::string> prefixes = {"extra_exit."};
+  for (size_t k = 0; k < m->lw.size(); ++k)
+    prefixes.push_back(k + 1 < m->lw.size() ? "lm_exit_modules." + std::to_string(k) + "." : std::string("lm_head."));
+  for (const std::string& p : prefixes) {
+    m->hflat.emplace_back();
+    HeadFlat& F = m->hflat.back();
+    auto add = [&](const std::string& name, long numel, int decays) {
+      const long o = F.total;
+      F.e.push_back({p + name, o, numel, decays});
+      F.total += (numel + 63) & ~63L;
+      return (size_t)o;
+    };
+    F.lstm.resize(m->Lh);
+    int in_f = d;
+    for (int l = 0; l < m->Lh; ++l) {
+      LstmW& Lw = F.lstm[l];
+      const std::string r = c.lstm_layernorm ? "rnn.layers." + std::to_string(3 * l) + "." : std::string("rnn.");
+      const std::string sfx = c.lstm_layernorm ? std::string("_l0") : "_l" + std::to_string(l);
+      Lw.wih = add(r + "weight_ih" + sfx, 4L * H * in_f, 1);
+      Lw.whh = add(r + "weight_hh" + sfx, 4L * H * H, 1);
+      Lw.bih = add(r + "bias_ih" + sfx, 4L * H, 0);
+      Lw.bhh = add(r + "bias_hh" + sfx, 4L * H, 0);
+      Lw.lnw = Lw.lnb = SIZE_MAX;
+      if (c.lstm_layernorm) {
+        Lw.lnw = add("rnn.layers." + std::to_string(3 * l + 1) + ".weight", H, 0);
+        Lw.lnb = add("rnn.layers." + std::to_string(3 * l + 1) + ".bias", H, 0);
+      }
+      in_f = H;
+    }
+    F.fc.resize(m->n_fc);
+    const char* heads[2] = {"actions", "gripper"};
+    for (int g = 0; g < 2; ++g) {
+      int cur = H;
+      for (int i = 0; i < m->n_fc; ++i) {
+        const std::string li = std::string(heads[g]) + ".mlp." + std::to_string(1 + 4 * i) + ".";
+        const std::string ni = std::string(heads[g]) + ".mlp." + std::to_string(2 + 4 * i) + ".";
+        F.fc[i].w[g] = add(li + "weight", (long)m->fc_dims[i] * cur, 1);
+        F.fc[i].b[g] = add(li + "bias", m->fc_dims[i], 0);
+        F.fc[i].lnw[g] = F.fc[i].lnb[g] = SIZE_MAX;
+        if (c.mlp_layernorm) {
+          F.fc[i].lnw[g] = add(ni + "weight", m->fc_dims[i], 0);
+          F.fc[i].lnb[g] = add(ni + "bias", m->fc_dims[i], 0);
+        }
+        cur = m->fc_dims[i];
+      }
+      const std::string lo = std::string(heads[g]) + ".mlp." + std::to_string(1 + 4 * m->n_fc) + ".";
+      const int n_out = g == 0 ? 6 * A : A;
+      (g == 0 ? F.wa : F.wg) = add(lo + "weight", (long)n_out * cur, 1);
+      (g == 0 ? F.ba : F.bg) = add(lo + "bias", n_out, 0);
+    }
   }
 }
 
@@ -1558,6 +1632,7 @@ int deer_model_create(const deer_config* cfg, deer_model** out) {
   const int dims[3] = {1024, 512, 256};                      // action_head.py:87-89
   for (int i = 0; i < 3; ++i) m->fc_dims[i] = dims[i];
   build_arena(m);
+  build_head_flat(m);
   build_workspace(m);
   // default controller: exits every exit_interval layers + the last layer (flamingo_mpt.py:239-250,268-270)
   for (int i = c.exit_interval - 1; i < c.n_layers - 1; i += c.exit_interval) m->exit_ids.push_back(i);
@@ -1588,6 +1663,7 @@ void deer_model_destroy(deer_model* m) {
   if (m->seq_scratch != nullptr) (void)hipFree(m->seq_scratch);
   if (m->calib_scratch != nullptr) (void)hipFree(m->calib_scratch);
   if (m->exit_scratch != nullptr) (void)hipFree(m->exit_scratch);
+  if (m->grad_scratch != nullptr) (void)hipFree(m->grad_scratch);
   delete m;
 }
 
@@ -1923,6 +1999,187 @@ int deer_head_sequence(deer_model* m, int head, const float* feats, int N, int L
   return deer_head_sequence_ex(m, head, feats, N, L, T, h0, c0, state, flags, actions, h_n, c_n, nullptr, nullptr, stream);
 }
 
+// ---- exit-only fine-tuning of one head (csrc/head_grad.hip) ----------------------------------------------------------------------------
+int deer_head_param_count(const deer_model* m, int head) {
+  if (m == nullptr || head < 0 || head >= (int)m->hflat.size()) return -1;
+  return (int)m->hflat[head].e.size();
+}
+
+int deer_head_param_entry(const deer_model* m, int head, int i, char* name, int name_len, long* offset, long* numel, int* decays) {
+  if (m == nullptr || head < 0 || head >= (int)m->hflat.size()) return DEER_ERR_SHAPE;
+  const HeadFlat& F = m->hflat[head];
+  if (i == -1) {
+    if (offset) *offset = 0;
+    if (numel) *numel = F.total;
+    return DEER_OK;
+  }
+  if (i < 0 || i >= (int)F.e.size()) return DEER_ERR_SHAPE;
+  const HeadParam& e = F.e[i];
+  if (name != nullptr && name_len > 0) {
+    strncpy(name, e.name.c_str(), (size_t)name_len - 1);
+    name[name_len - 1] = 0;
+  }
+  if (offset) *offset = e.offset;
+  if (numel) *numel = e.numel;
+  if (decays) *decays = e.decays;
+  return DEER_OK;
+}
+
+// Linear backward on R rows: dW (+)= dY^T X, db (+)= colsum(dY), and (dx != NULL) dX (+)= dY W (torch.nn.Linear's autograd)
+static int head_grad_linear(const float* dy, long ld_dy, const float* x, long ld_x, const float* w, float* gw, float* gb, float* gb2, float* dx,
+                            long ld_dx, int dx_acc, int R, int n_out, int n_in, int acc, void* stream) {
+  DEER_TRY(deer_head_grad_gemm(dy, ld_dy, 1, x, ld_x, 1, gw, n_in, n_out, n_in, R, acc, stream));
+  DEER_TRY(deer_head_grad_colsum(dy, ld_dy, nullptr, 0, nullptr, gb, gb2, nullptr, R, n_out, acc, stream));
+  if (dx != nullptr) DEER_TRY(deer_head_grad_gemm(dy, ld_dy, 0, w, n_in, 1, dx, ld_dx, R, n_in, n_out, dx_acc, stream));
+  return DEER_OK;
+}
+
+int deer_head_loss_grad(deer_model* m, int head, const float* params, const float* X, int N, int L, const float* pose, const float* grip01,
+                        float w_bin, float scale, float* grad, int accumulate, float* loss_out, void* stream) {
+  if (m == nullptr || params == nullptr || X == nullptr || pose == nullptr || grip01 == nullptr || grad == nullptr) return DEER_ERR_SHAPE;
+  if (N <= 0 || L <= 0 || (long)N * L > kSeqRows) return DEER_ERR_SHAPE;
+  const deer_config& c = m->c;
+  if (c.multi_step_action < 0 || c.multi_step_action > 8 || head < 0 || head >= (int)m->hflat.size()) return DEER_ERR_SHAPE;
+  if (c.use_state) {
+    fprintf(stderr, "deer_head_loss_grad: a use_state head would need gradients for its state embeddings (embed_arm_state, "
+                    "embed_gripper_state, embed_state); they are not built\n");
+    return DEER_ERR_SHAPE;
+  }
+  const HeadFlat& F = m->hflat[head];
+  const int d = m->d, H = m->H, Lh = m->Lh, A = std::max(1, c.multi_step_action), n_fc = m->n_fc, R = N * L;
+  if ((d & 7) || (H & 15)) return DEER_ERR_SHAPE;
+  const bool lln = c.lstm_layernorm != 0, mln = c.mlp_layernorm != 0;
+  const int fc_max = n_fc > 0 ? m->fc_dims[0] : H;
+  const long wmax = std::max(fc_max, H);
+  // scratch (floats).  Tape: per LSTM layer gates [R][4H], c [R][H], raw h [R][H], LN(h) [R][H] + stats [R][2]; per MLP head and hidden
+  // layer pre-LN [R][dim], stats, ReLU output [R][dim]; outputs [R][8A].  Backward: dz [R][8A], num / bin [R], two ping-pong buffers
+  // [R][max(fc, H)], dX of the LSTM output [R][H], dG [R][4H], dc [N][H], H_prev [R][H].
+  long n_tape = 0;
+  for (int l = 0; l < Lh; ++l) n_tape += (long)R * (4 * H + 3 * H + 2) + 4 * 64;
+  for (int fi = 0; fi < n_fc; ++fi) n_tape += 2 * ((long)R * (2 * m->fc_dims[fi] + 2) + 3 * 64);
+  const size_t need = (size_t)(n_tape + 2L * R * 8 * A + 2L * R + 2 * R * wmax + (long)R * H + (long)R * 4 * H + (long)N * H + (long)R * H) *
+                          sizeof(float) + 256 * 256;   // + the 256-byte rounding of every block
+  hipStream_t st = (hipStream_t)stream;
+  if (!grow_scratch(m->grad_scratch, m->grad_bytes, need, st)) return DEER_ERR_LAUNCH;
+  ScratchTake take{reinterpret_cast<char*>(m->grad_scratch)};
+  std::vector<float*> G(Lh), C(Lh), Y(Lh), XN(Lh), ST(Lh);
+  for (int l = 0; l < Lh; ++l) {
+    G[l] = take((long)R * 4 * H);
+    C[l] = take((long)R * H);
+    Y[l] = take((long)R * H);
+    XN[l] = lln ? take((long)R * H) : Y[l];
+    ST[l] = lln ? take(2L * R) : nullptr;
+  }
+  float *ZP[2][3] = {}, *ZA[2][3] = {}, *ZS[2][3] = {};
+  for (int g = 0; g < 2; ++g)
+    for (int fi = 0; fi < n_fc; ++fi) {
+      ZA[g][fi] = take((long)R * m->fc_dims[fi]);
+      ZP[g][fi] = mln ? take((long)R * m->fc_dims[fi]) : nullptr;
+      ZS[g][fi] = mln ? take(2L * R) : nullptr;
+    }
+  float* OUT = take((long)R * 8 * A);
+  float* DZ = take((long)R * 8 * A);
+  float* NUM = take(R);
+  float* BIN = take(R);
+  float* DB[2] = {take(R * wmax), take(R * wmax)};
+  float* DXO = take((long)R * H);
+  float* DG = take((long)R * 4 * H);
+  float* DC = take((long)N * H);
+  float* HP = take((long)R * H);
+  auto Pp = [&](size_t off) { return off == SIZE_MAX ? nullptr : params + off; };
+  auto Gp = [&](size_t off) { return off == SIZE_MAX ? nullptr : grad + off; };
+
+  // ---- taped forward: the LSTM, layer by layer ----
+  for (int l = 0; l < Lh; ++l) {
+    const LstmW& Lw = F.lstm[l];
+    const float* xin = l == 0 ? X : XN[l - 1];
+    const int in_dim = l == 0 ? d : H;
+    DEER_TRY(deer_head_seq_gemm(xin, in_dim, Pp(Lw.wih), 1, Pp(Lw.bih), G[l], 4L * H, R, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+    for (int t = 0; t < L; ++t)
+      DEER_TRY(deer_head_grad_lstm_step(G[l] + (long)t * 4 * H, (long)L * 4 * H, t > 0 ? Y[l] + (long)(t - 1) * H : nullptr, (long)L * H, Pp(Lw.whh),
+                                        Pp(Lw.bhh), t > 0 ? C[l] + (long)(t - 1) * H : nullptr, C[l] + (long)t * H, (long)L * H,
+                                        Y[l] + (long)t * H, (long)L * H, N, H, stream));
+    if (lln) DEER_TRY(deer_head_grad_ln(Y[l], H, XN[l], H, Pp(Lw.lnw), Pp(Lw.lnb), ST[l], R, H, kEps, 0, stream));
+  }
+  const float* XO = XN[Lh - 1];
+  // ---- taped forward: the two MLP heads (action_head.py:86-136) ----
+  for (int g = 0; g < 2; ++g) {
+    const float* src = XO;
+    int kin = H;
+    for (int fi = 0; fi < n_fc; ++fi) {
+      const FcW& W = F.fc[fi];
+      const int dim = m->fc_dims[fi];
+      if (mln) {
+        DEER_TRY(deer_head_seq_gemm(src, kin, Pp(W.w[g]), 1, Pp(W.b[g]), ZP[g][fi], dim, R, dim, kin, DEER_SEQ_EPI_NONE, stream));
+        DEER_TRY(deer_head_grad_ln(ZP[g][fi], dim, ZA[g][fi], dim, Pp(W.lnw[g]), Pp(W.lnb[g]), ZS[g][fi], R, dim, kEps, 1, stream));
+      } else {
+        DEER_TRY(deer_head_seq_gemm(src, kin, Pp(W.w[g]), 1, Pp(W.b[g]), ZA[g][fi], dim, R, dim, kin, DEER_SEQ_EPI_RELU, stream));
+      }
+      src = ZA[g][fi];
+      kin = dim;
+    }
+    if (g == 0) DEER_TRY(deer_head_seq_gemm(src, kin, Pp(F.wa), 1, Pp(F.ba), OUT, 8L * A, R, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
+    else DEER_TRY(deer_head_seq_gemm(src, kin, Pp(F.wg), 1, Pp(F.bg), OUT + 6 * A, 8L * A, R, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
+  }
+  // ---- loss value and d loss / d (pre-tanh pose, logit) ----
+  float* LOSS = loss_out != nullptr ? loss_out : DC;           // DC is free until the backward's first recurrent step
+  DEER_TRY(deer_head_grad_loss(OUT, pose, grip01, R, A, w_bin, scale, DZ, NUM, BIN, LOSS, stream));
+  // ---- backward: the MLP heads; their input gradients meet in DXO ----
+  for (int g = 0; g < 2; ++g) {
+    const int n_out = g == 0 ? 6 * A : A;
+    const float* dy = DZ + (g == 0 ? 0 : 6 * A);
+    long ld_dy = 8L * A;
+    const size_t ow = g == 0 ? F.wa : F.wg, ob = g == 0 ? F.ba : F.bg;
+    int cur = 0;                                               // ping-pong buffer that receives the next dX
+    {
+      const float* src = n_fc > 0 ? ZA[g][n_fc - 1] : XO;
+      const int kin = n_fc > 0 ? m->fc_dims[n_fc - 1] : H;
+      float* dx = n_fc > 0 ? DB[cur] : DXO;
+      DEER_TRY(head_grad_linear(dy, ld_dy, src, kin, Pp(ow), Gp(ow), Gp(ob), nullptr, dx, kin, n_fc > 0 ? 0 : g, R, n_out, kin, accumulate, stream));
+    }
+    for (int fi = n_fc - 1; fi >= 0; --fi) {
+      const FcW& W = F.fc[fi];
+      const int dim = m->fc_dims[fi];
+      float* dz = DB[cur];                                     // d loss / d ReLU output [R][dim]
+      DEER_TRY(deer_head_grad_relu_mask(dz, ZA[g][fi], (long)R * dim, stream));
+      if (mln) {
+        DEER_TRY(deer_head_grad_colsum(dz, dim, ZP[g][fi], dim, ZS[g][fi], Gp(W.lnb[g]), nullptr, Gp(W.lnw[g]), R, dim, accumulate, stream));
+        DEER_TRY(deer_head_grad_ln_bwd(dz, dim, ZP[g][fi], dim, ZS[g][fi], Pp(W.lnw[g]), dz, dim, R, dim, stream));
+      }
+      const float* src = fi > 0 ? ZA[g][fi - 1] : XO;
+      const int kin = fi > 0 ? m->fc_dims[fi - 1] : H;
+      float* dx = fi > 0 ? DB[cur ^ 1] : DXO;
+      DEER_TRY(head_grad_linear(dz, dim, src, kin, Pp(W.w[g]), Gp(W.w[g]), Gp(W.b[g]), nullptr, dx, kin, fi > 0 ? 0 : g, R, dim, kin, accumulate,
+                                stream));
+      cur ^= 1;
+    }
+  }
+  // ---- backward through time, from the top LSTM layer down; DXO holds d loss / d (the layer's output) ----
+  for (int l = Lh - 1; l >= 0; --l) {
+    const LstmW& Lw = F.lstm[l];
+    if (lln) {
+      DEER_TRY(deer_head_grad_colsum(DXO, H, Y[l], H, ST[l], Gp(Lw.lnb), nullptr, Gp(Lw.lnw), R, H, accumulate, stream));
+      DEER_TRY(deer_head_grad_ln_bwd(DXO, H, Y[l], H, ST[l], Pp(Lw.lnw), DXO, H, R, H, stream));
+    }
+    for (int t = L - 1; t >= 0; --t)
+      DEER_TRY(deer_head_grad_lstm_bwd_step(DXO + (long)t * H, (long)L * H, t < L - 1 ? DG + (long)(t + 1) * 4 * H : nullptr, G[l] + (long)t * 4 * H,
+                                            DG + (long)t * 4 * H, (long)L * 4 * H, Pp(Lw.whh), C[l] + (long)t * H,
+                                            t > 0 ? C[l] + (long)(t - 1) * H : nullptr, (long)L * H, DC, N, H, stream));
+    // H_prev[n][t] = h_{t-1} (zero at t = 0)
+    if (hipMemset2DAsync(HP, (size_t)L * H * sizeof(float), 0, (size_t)H * sizeof(float), N, st) != hipSuccess) return DEER_ERR_LAUNCH;
+    if (L > 1 && hipMemcpy2DAsync(HP + H, (size_t)L * H * sizeof(float), Y[l], (size_t)L * H * sizeof(float), (size_t)(L - 1) * H * sizeof(float), N,
+                                  hipMemcpyDeviceToDevice, st) != hipSuccess)
+      return DEER_ERR_LAUNCH;
+    const float* xin = l == 0 ? X : XN[l - 1];
+    const int in_dim = l == 0 ? d : H;
+    DEER_TRY(deer_head_grad_gemm(DG, 4L * H, 1, xin, in_dim, 1, Gp(Lw.wih), in_dim, 4 * H, in_dim, R, accumulate, stream));
+    DEER_TRY(deer_head_grad_gemm(DG, 4L * H, 1, HP, H, 1, Gp(Lw.whh), H, 4 * H, H, R, accumulate, stream));
+    DEER_TRY(deer_head_grad_colsum(DG, 4L * H, nullptr, 0, nullptr, Gp(Lw.bih), Gp(Lw.bhh), nullptr, R, 4 * H, accumulate, stream));
+    if (l > 0) DEER_TRY(deer_head_grad_gemm(DG, 4L * H, 0, Pp(Lw.wih), H, 1, DXO, H, R, H, 4 * H, 0, stream));
+  }
+  return DEER_OK;
+}
+
 // ---- threshold calibration as one device pass (csrc/calib.hip) ------------------------------------------------------------------------
 // candidate layers [0] + exits (value_net.py:139: `for i in [0] + self.exit_list`); -1: no exits / layer 0 among them (value_net.py:135)
 static int calib_layers(const deer_model* m, int* lay) {
@@ -2099,7 +2356,7 @@ int deer_exit_outputs(deer_model* m, const float* P, int T, const int* sel, cons
 
 int deer_exit_n_heads(const deer_model* m) { return (m->lw.empty() ? 0 : (int)m->lw.size() - 1) + 3; }
 
-long deer_model_scratch_bytes(const deer_model* m) { return (long)(m->seq_bytes + m->calib_bytes + m->exit_bytes); }
+long deer_model_scratch_bytes(const deer_model* m) { return (long)(m->seq_bytes + m->calib_bytes + m->exit_bytes + m->grad_bytes); }
 
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream) {
   if (m->ws == nullptr || T <= 0 || T > m->c.max_text_len || m->B * T > kMaxRows || exit_id >= m->c.n_layers) return DEER_ERR_SHAPE;

@@ -1152,6 +1152,29 @@ class DeerEngine:
         from .ops import run_exit_losses
         return run_exit_losses(self.lib, self.cfg, actions.to(device=self.dev), torch.as_tensor(pose), torch.as_tensor(grip01), w_bin)
 
+    def head_trainer(self, state_dict, **kw):
+        """A ``finetune.HeadTrainer`` over this engine: exit-only fine-tuning (train_utils.py:487-543 with only_train_head) of the heads in
+        ``state_dict`` on pooled features; the engine's weights do not change until the trainer's ``commit()``."""
+        from .finetune import HeadTrainer
+        return HeadTrainer(self, state_dict, **kw)
+
+    def reload_tensors(self, sd: Dict[str, torch.Tensor]):
+        """Re-ingests tensors of the reference state dict into the weight arena (``deer_model_load_tensor``; unknown names raise).  Every
+        engine over the same arena (the owner, its siblings) is told that its head pre-pass is stale: the W_hh h + b_hh halves
+        ``deer_begin_step`` left were computed from the old weights, so evaluations enqueued before the next ``deer_begin_step`` read W_hh
+        themselves.  Captured graphs read the arena at replay: nothing is recaptured."""
+        st = _cur_stream()
+        for name, t in sd.items():
+            if not self.lib.deer_model_knows_tensor(self._h, name.encode()):
+                raise KeyError(f"reload_tensors: {name} is no parameter of this model")
+            src = t.detach().to(device=self.dev, dtype=torch.float32).contiguous()
+            abi.check(self.lib.deer_model_load_tensor(self._h, name.encode(), abi.ptr(src), 0, src.numel(), st),
+                      f"deer_model_load_tensor({name}, shape {tuple(t.shape)})")
+            torch.cuda.current_stream().synchronize()            # src may be freed once the conversion ran
+        root = getattr(self, "_weights_owner", None) or self
+        for e in [root] + list(root._siblings.values()):
+            e._head_state_changed()
+
     def _head_eval(self, feats: torch.Tensor, commit: bool) -> torch.Tensor:
         """One DeterministicDecoder step of all n_envs sequences on ``feats`` (n_envs*T, d) from the current LSTM state; commit=True
         stores the new state (update_hidden_state protocol, action_head.py:548-558).  Returns the device rows [pose6, gripper prob,

@@ -10,6 +10,9 @@ One batch is what the reference's CALVIN loader yields, by name:
 The frames go through ``MPTFlamingo.all_exit_actions`` (one static full-depth pass + ``DeerEngine.exit_outputs``), the losses through
 ``DeerEngine.exit_losses``; the per-head sums stay on the device until the end.
 
+``finetune_exit_heads`` is the other half of that step for a frozen trunk (``only_train_head``): the same features, then gradient and
+AdamW on the device (``finetune.HeadTrainer``).
+
 ``on_policy_values`` is the other evaluation without labels: the exit values of a live rollout (shadow steps logged on the device), the
 input of ``value_net.calibrate_on_policy``.
 """
@@ -88,6 +91,40 @@ def exit_losses_on_windows(model, batches: Iterable[Dict[str, torch.Tensor]], w_
     names = [f"exit{k}" for k in range(n_layer_heads)] + ["final", "extra", "extra2"]
     return {"heads": names, "num": means[0].tolist(), "bin": means[1].tolist(), "loss": means[2].tolist(),
             "total": float((means[2] * w).sum()), "rows": count, "w_bin": float(w_bin)}
+
+
+def finetune_exit_heads(model, batches: Iterable[Dict[str, torch.Tensor]], steps: int, state_dict: Dict[str, torch.Tensor], lr: float = 1e-4,
+                        w_bin: float = 0.01, generator: Optional[torch.Generator] = None, weights: Optional[Sequence[float]] = None,
+                        commit: bool = True, **trainer_kw):
+    """Exit-only fine-tuning on demonstration windows: the reference's second stage (train_utils.py:487-543 with only_train_head /
+    no_backbone_grad, AdamW over the heads alone, train_calvin_post_strategy.py:466-535) with the trunk frozen.  The pooled exit-layer
+    features of every batch are computed ONCE (``window_exit_pooled``; the trunk never changes), then ``steps`` optimizer steps cycle
+    over the batches: layer tables drawn per step like ``exit_losses_on_windows`` draws them, ``HeadTrainer.loss_and_grads``, ``step``.
+    ``state_dict`` holds the heads' current tensors (the checkpoint the model was built from); trainer_kw: ``finetune.HeadTrainer``'s
+    (heads, weight_decay, betas, eps, exit_decay).  Returns (trainer, losses (steps, Hn) on the device); commit=True re-ingests the trained
+    heads into the model's engine at the end."""
+    e = model.engine
+    A, Wn = e.A, model.window_size
+    feats = []
+    for batch in batches:
+        pose, grip01 = split_labels(batch["labels"], A)
+        kw = window_batch_inputs(batch, Wn)
+        bs, rgb, grip_f, ids, mask, _ = model._window_inputs(kw["vision_x"], kw["lang_x"], kw["attention_mask"], kw["vision_gripper"], kw["state_tensor"])
+        pooled = e.window_exit_pooled(rgb, grip_f, ids, mask)
+        feats.append((pooled.view(bs, Wn, pooled.shape[1], pooled.shape[2]).clone(), pose.to(e.dev), grip01.to(e.dev)))
+    if not feats:
+        raise ValueError("finetune_exit_heads: no batches")
+    trainer = e.head_trainer(state_dict, lr=lr, **trainer_kw)
+    history = []
+    for k in range(int(steps)):
+        P, pose, grip01 = feats[k % len(feats)]
+        rl, tl = model.draw_exit_layers(P.shape[0], Wn, generator)
+        trainer.zero_grad()
+        history.append(trainer.loss_and_grads(P, rl, tl, pose, grip01, w_bin=w_bin, weights=weights))
+        trainer.step()
+    if commit:
+        trainer.commit()
+    return trainer, (torch.stack(history) if history else torch.empty(0, device=e.dev))
 
 
 def on_policy_values(wrapper, envs, eval_sequences, annotations, task_checker, controller, n_samples: int, ep_len: Optional[int] = None):

@@ -22,6 +22,14 @@ through PyTorch-ROCm custom ops").  These are the three coarse operators SURVEY.
                                                                                (value_net.py:120-133), one column per environment of
                                                                                active_mask, appended to a device value matrix; model-free
 
+  deer::head_loss_grad(Tensor params, Tensor feats, Tensor pose, Tensor grip01, int model, int head, float w_bin, float scale,
+                       Tensor(a!) grad, bool accumulate) -> Tensor loss        one head's loss and parameter gradients with a frozen
+                                                                               trunk (train_utils.py:487-543, only_train_head) from a flat
+                                                                               f32 parameter buffer; taped forward + backward on the device
+  deer::adamw_step(Tensor(a!) param, Tensor grad, Tensor(b!) m, Tensor(c!) v, Tensor seg_end, Tensor seg_decay, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int step) -> () torch.optim.AdamW over flat buffers
+                                                                               (train_calvin_post_strategy.py:535); model-free
+
 ``model`` is the address of a ``deer_model`` (``NativeModel.handle``): weights, workspace, LSTM state and the exit controller
 configuration live in that object, like they live in the reference's stateful ``MPTFlamingo`` module.
 There is no CPU implementation: the ops raise without a HIP device / without the library.
@@ -510,6 +518,119 @@ def value_log_append(ctl: torch.Tensor, n_envs: int, n_exit: int, active_mask: i
 @value_log_append.register_fake
 def _(ctl, n_envs, n_exit, active_mask, values, capacity, taken, state):
     value_log_shapes(ctl, n_envs, n_exit, active_mask, values, capacity, taken, state)
+
+
+MAX_GRAD_ROWS = 2048       # rows (N * L) of one deer_head_loss_grad call (csrc/model.hip kSeqRows); longer batches are chunked by the caller
+
+
+def head_param_table(lib, handle, head: int):
+    """The spine's table of one head's trainable tensors (``deer_head_param_entry``, host only): ([(name, offset, numel, decays)] in the
+    reference's state-dict order, floats of the flat buffer).  head 0 = extra_exit, k >= 1 = per-layer head k."""
+    n = lib.deer_head_param_count(handle, int(head))
+    if n < 0:
+        raise ValueError(f"head {head}: the model has no such head")
+    name = ctypes.create_string_buffer(256)
+    off, numel, dec = ctypes.c_long(), ctypes.c_long(), ctypes.c_int()
+    out = []
+    for i in range(n):
+        abi.check(lib.deer_head_param_entry(handle, int(head), i, name, len(name), ctypes.byref(off), ctypes.byref(numel), ctypes.byref(dec)),
+                  "deer_head_param_entry")
+        out.append((name.value.decode(), off.value, numel.value, bool(dec.value)))
+    abi.check(lib.deer_head_param_entry(handle, int(head), -1, None, 0, ctypes.byref(off), ctypes.byref(numel), None), "deer_head_param_entry")
+    return out, numel.value
+
+
+def head_loss_grad_shapes(cfg, total: int, params, feats_shape, pose_shape, grip_shape, grad):
+    """Host-side checks of one loss-gradient call (no device touched): params / grad flat float32 buffers of ``total`` values, feats
+    (N, L, d) pooled rows, pose N L x 6 A, grip01 N L x A.  Returns (N, L, A)."""
+    if getattr(cfg, "use_state", False):
+        raise NotImplementedError("head_loss_grad: a use_state head would need gradients for its state embeddings (embed_arm_state, "
+                                  "embed_gripper_state, embed_state); they are not built")
+    A = max(1, int(getattr(cfg, "multi_step_action", 1)))
+    if len(feats_shape) != 3 or int(feats_shape[2]) != cfg.d_model:
+        raise ValueError(f"head_loss_grad: feats must be (N, L, d = {cfg.d_model}) pooled rows, got {tuple(feats_shape)}")
+    N, L = int(feats_shape[0]), int(feats_shape[1])
+    if N < 1 or L < 1 or N * L > MAX_GRAD_ROWS:
+        raise ValueError(f"head_loss_grad: {N} x {L} rows; one call takes 1..{MAX_GRAD_ROWS} (chunk whole sequences with accumulate=True)")
+    for name, t in (("params", params), ("grad", grad)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != total or not t.is_contiguous():
+            raise ValueError(f"head_loss_grad: {name} must be a contiguous float32 buffer of {total} values, got {tuple(t.shape)} {t.dtype}")
+    n_pose, n_grip = 1, 1
+    for v in pose_shape:
+        n_pose *= int(v)
+    for v in grip_shape:
+        n_grip *= int(v)
+    if n_pose != N * L * 6 * A or n_grip != N * L * A:
+        raise ValueError(f"head_loss_grad: labels pose {tuple(pose_shape)} / gripper {tuple(grip_shape)} do not hold {6 * A} / {A} values for each "
+                         f"of the {N * L} rows")
+    return N, L, A
+
+
+def run_head_loss_grad(lib, handle, cfg, head: int, params: torch.Tensor, feats: torch.Tensor, pose, grip01, w_bin: float, scale: float,
+                       grad: torch.Tensor, accumulate: bool, loss_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One ``deer_head_loss_grad`` call on the current stream: grad (+)= scale d loss / d params, returns the (1,) loss of the call's rows
+    on the device (written into ``loss_out`` when given); nothing is synchronised."""
+    _, total = head_param_table(lib, handle, head)
+    N, L, A = head_loss_grad_shapes(cfg, total, params, feats.shape, pose.shape, grip01.shape, grad)
+    dev = params.device
+    f = feats.to(device=dev, dtype=torch.float32).contiguous()
+    p = pose.to(device=dev, dtype=torch.float32).contiguous()
+    g = grip01.to(device=dev, dtype=torch.float32).contiguous()
+    loss = loss_out if loss_out is not None else torch.empty(1, dtype=torch.float32, device=dev)
+    abi.check(lib.deer_head_loss_grad(handle, int(head), abi.ptr(params), abi.ptr(f), N, L, abi.ptr(p), abi.ptr(g), float(w_bin), float(scale),
+                                      abi.ptr(grad), 1 if accumulate else 0, abi.ptr(loss), _stream()), "deer_head_loss_grad")
+    return loss
+
+
+@torch.library.custom_op("deer::head_loss_grad", mutates_args=("grad",), device_types="cuda")
+def head_loss_grad(params: torch.Tensor, feats: torch.Tensor, pose: torch.Tensor, grip01: torch.Tensor, model: int, head: int, w_bin: float,
+                   scale: float, grad: torch.Tensor, accumulate: bool) -> torch.Tensor:
+    """params / grad: flat f32 buffers laid out by ``head_param_table``; feats (N, L, d) pooled rows of N windows; pose (N, L, 6 A), grip01
+    (N, L, A) labels -> the (1,) loss mean_rows(Huber + w_bin BCE) (train_utils.py:519-540); grad (+)= scale d loss / d params."""
+    m = _model(model)
+    return run_head_loss_grad(m.lib, m._h, m.cfg, head, params, feats, pose, grip01, w_bin, scale, grad, accumulate)
+
+
+@head_loss_grad.register_fake
+def _(params, feats, pose, grip01, model, head, w_bin, scale, grad, accumulate):
+    return params.new_empty((1,), dtype=torch.float32)
+
+
+def adamw_shapes(param, grad, m, v, seg_end, seg_decay, step: int):
+    """Host-side checks of one AdamW launch (no device touched).  Returns (numel, n_seg)."""
+    n = param.numel()
+    for name, t in (("param", param), ("grad", grad), ("m", m), ("v", v)):
+        if t.dtype != torch.float32 or t.dim() != 1 or t.numel() != n or not t.is_contiguous():
+            raise ValueError(f"adamw_step: {name} must be a contiguous float32 buffer of {n} values, got {tuple(t.shape)} {t.dtype}")
+    if n < 1:
+        raise ValueError("adamw_step: empty buffers")
+    if seg_end.dtype != torch.int32 or seg_decay.dtype != torch.int32 or seg_end.shape != seg_decay.shape or seg_end.dim() != 1:
+        raise ValueError(f"adamw_step: seg_end / seg_decay must be int32 vectors of one length, got {tuple(seg_end.shape)} {seg_end.dtype} / "
+                         f"{tuple(seg_decay.shape)} {seg_decay.dtype}")
+    if step < 1:
+        raise ValueError(f"adamw_step: step counts from 1, got {step}")
+    return n, int(seg_end.numel())
+
+
+def run_adamw_step(lib, param, grad, m, v, seg_end, seg_decay, lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int):
+    """One ``deer_adamw_step`` launch on the current stream (csrc/head_grad.hip); nothing is synchronised or allocated."""
+    n, n_seg = adamw_shapes(param, grad, m, v, seg_end, seg_decay, step)
+    hyper = (ctypes.c_double * 5)(float(lr), float(beta1), float(beta2), float(eps), float(weight_decay))     # read on the host during the call
+    abi.check(lib.deer_adamw_step(abi.ptr(param), abi.ptr(grad), abi.ptr(m), abi.ptr(v), n, abi.ptr(seg_end) if n_seg else None,
+                                  abi.ptr(seg_decay) if n_seg else None, n_seg, hyper, int(step), _stream()), "deer_adamw_step")
+
+
+@torch.library.custom_op("deer::adamw_step", mutates_args=("param", "m", "v"), device_types="cuda")
+def adamw_step(param: torch.Tensor, grad: torch.Tensor, m: torch.Tensor, v: torch.Tensor, seg_end: torch.Tensor, seg_decay: torch.Tensor,
+               lr: float, beta1: float, beta2: float, eps: float, weight_decay: float, step: int) -> None:
+    """torch.optim.AdamW's update of flat f32 buffers in one launch; seg_end / seg_decay (int32, device): ascending exclusive segment ends and
+    their decay flags (biases and norms 0) - empty: every element decays."""
+    run_adamw_step(abi.lib(), param, grad, m, v, seg_end, seg_decay, lr, beta1, beta2, eps, weight_decay, step)
+
+
+@adamw_step.register_fake
+def _(param, grad, m, v, seg_end, seg_decay, lr, beta1, beta2, eps, weight_decay, step):
+    adamw_shapes(param, grad, m, v, seg_end, seg_decay, step)
 
 
 def decode_ctl(ctl: torch.Tensor):

@@ -452,6 +452,52 @@ int deer_window_gather_layers(const float* P, const int* sel, const int* slot_of
                               int d, void* stream);
 int deer_exit_losses(const float* actions, const float* pose, const float* grip01, int Hn, long R, int A, float w_bin, float* num, float* bin,
                      float* loss, void* stream);
+/* ---- exit-only fine-tuning of one head (csrc/head_grad.hip): the backward half of the multi-exit step with a frozen trunk
+ * (only_train_head / no_backbone_grad, robot_flamingo/train/train_utils.py:487-543) and its optimizer (train_calvin_post_strategy.py:535) ----
+ * Pieces that deer_head_loss_grad (deer_model.h) chains with deer_head_seq_gemm on f32 weight rows.  f32 arithmetic, fixed summation
+ * orders, no atomics (two runs give identical bits); no dropout.
+ * deer_head_grad_ln            deer_head_seq_ln (LayerNormLSTM action_head.py:44-53, MLP LayerNorm :97-103) that also keeps stats [M][2] =
+ *                              (mean, rstd) of every row for the backward
+ * deer_head_grad_lstm_step     deer_head_seq_lstm_step (one nn.LSTM step over N rows, gate order i, f, g, o) on f32 W_hh [4H][H] with a tape:
+ *                              gates [N rows, pitch ld_g][4H] holds x W_ih^T + b_ih on entry and the ACTIVATED gates on return; c_out / h_out
+ *                              receive c_t and the raw h_t; h_prev / c_prev both NULL at t = 0 (zero state).  H % 16 == 0.
+ * deer_head_grad_loss          loss = mean_rows( mean_6A Huber_1(pose - label) + w_bin mean_A BCEwithlogits(logit, target) ) of one head
+ *                              (train_utils.py:519-540) in deer_exit_losses' arithmetic and order (num, bin [R], loss [1]), and
+ *                              dz [R][8 A] = d (scale loss) / d [pre-tanh pose 6 A | gripper logit A | 0 A] (autograd of :519-543; scale =
+ *                              exit weight x accumulation share).  actions [R][8 A] = [pose 6 A | prob A | logit A].
+ * deer_head_grad_gemm          C[M][N] (+)= sum_k opA(m, k) opB(n, k), exact-f32 MFMA (v_mfma_f32_16x16x4_f32): ta / tb = 0 operand stored
+ *                              [rows][K], 1 stored [K][rows].  Linear backward: dX = dY W is (dY, ta 0; W, tb 1), dW = dY^T X is (dY, ta 1;
+ *                              X, tb 1) (torch.nn.Linear's autograd).  Any M, N, K; 16-byte accesses where pointer, pitch and extent allow.
+ * deer_head_grad_colsum        out_sum[c] (and out_sum2[c]) (+)= sum_m dy[m][c] (bias gradient, LayerNorm d beta); with x / stats:
+ *                              out_xhat[c] (+)= sum_m dy[m][c] (x[m][c] - mean_m) rstd_m (LayerNorm d gamma)
+ * deer_head_grad_relu_mask     dz[i] = act[i] > 0 ? dz[i] : 0 (ReLU backward from its output), n % 4 == 0 contiguous values
+ * deer_head_grad_ln_bwd        LayerNorm d input of M rows: dx = rstd (g - mean(g) - xhat mean(g xhat)), g = dy gamma; dx may be dy
+ * deer_head_grad_lstm_bwd_step one step of the LSTM's backward through time over N rows: dh_t = dh_ext + dG_{t+1} W_hh (dg_next NULL at the
+ *                              last step: no recurrent term and dc taken as zero), dG_t [.., pitch ld_g][4H] = the pre-activation gate
+ *                              gradients, dc [N][H] <- dc_{t-1}; gates / c_t / c_prev (NULL at t = 0) from the tape.  H % 16 == 0.
+ * deer_adamw_step              torch.optim.AdamW (_single_tensor_adamw) over flat f32 buffers: p <- p (1 - lr wd) on decaying segments,
+ *                              m, v moments, bias corrections 1 - beta^step, p <- p - lr / bc1 * m / (sqrt(v) / sqrt(bc2) + eps).  seg_end /
+ *                              seg_decay: DEVICE int32 [n_seg] ascending exclusive segment ends and decay flags (norms and biases: 0);
+ *                              n_seg = 0: every element decays; elements past the last end take no decay.  hyper: HOST double[5] = {lr,
+ *                              beta1, beta2, eps, weight_decay} - doubles, because torch forms 1 - beta and the bias corrections in
+ *                              Python floats before its f32 kernels see them (1 - 0.999f is off by 1.3e-5).  step >= 1. */
+int deer_head_grad_ln(const float* src, long ld_src, float* dst, long ld_dst, const float* w, const float* b, float* stats, int M, int n, float eps,
+                      int relu, void* stream);
+int deer_head_grad_lstm_step(float* gates, long ld_g, const float* h_prev, long ld_h, const float* w_hh, const float* b_hh, const float* c_prev,
+                             float* c_out, long ld_c, float* h_out, long ld_out, int N, int H, void* stream);
+int deer_head_grad_loss(const float* actions, const float* pose, const float* grip01, long R, int A, float w_bin, float scale, float* dz, float* num,
+                        float* bin, float* loss, void* stream);
+int deer_head_grad_gemm(const float* A, long lda, int ta, const float* B, long ldb, int tb, float* C, long ldc, int M, int N, int K, int accumulate,
+                        void* stream);
+int deer_head_grad_colsum(const float* dy, long ld, const float* x, long ldx, const float* stats, float* out_sum, float* out_sum2, float* out_xhat,
+                          int M, int n, int accumulate, void* stream);
+int deer_head_grad_relu_mask(float* dz, const float* act, long n, void* stream);
+int deer_head_grad_ln_bwd(const float* dy, long ld_dy, const float* x, long ld_x, const float* stats, const float* gamma, float* dx, long ld_dx,
+                          int M, int n, void* stream);
+int deer_head_grad_lstm_bwd_step(const float* dh_ext, long ld_dh, const float* dg_next, const float* gates, float* dg, long ld_g, const float* w_hh,
+                                 const float* c_t, const float* c_prev, long ld_c, float* dc, int N, int H, void* stream);
+int deer_adamw_step(float* param, const float* grad, float* m, float* v, long numel, const int* seg_end, const int* seg_decay, int n_seg,
+                    const double* hyper, int step, void* stream);
 /* ---- exit thresholds of many operating points from one calibration matrix (csrc/thresholds.hip): the solver of
  * ExitController.set_threshold, value_net.py:242-262 ----
  * values [n_stage][ld] f32 (n_sample deltas per row); out_n: DEVICE int32 [n_points][n_exit], the counts floor(n_sample * probs[e]) of

@@ -217,6 +217,33 @@ int deer_pool_window_layers(deer_model* m, int n_frames, int T, float* P, void* 
 int deer_exit_outputs(deer_model* m, const float* P, int T, const int* sel, const float* state, int bs, int W, float* actions, void* stream);
 int deer_exit_n_heads(const deer_model* m);
 long deer_model_scratch_bytes(const deer_model* m);
+/* Exit-only fine-tuning (csrc/head_grad.hip): the reference's second training stage - only_train_head / no_backbone_grad = True
+ * (train_utils.py:499), exit_optimizer = AdamW(get_grouped_params(only_head=True)) (train_calvin_post_strategy.py:466-535) - for ONE head on
+ * pooled features.  The trained parameters live OUTSIDE the weight arena, in a flat f32 buffer of the caller laid out by this table:
+ * deer_head_param_count  host only: number of parameter tensors of head (0 = extra_exit, k >= 1 = per-layer head k), -1: no such head
+ * deer_head_param_entry  host only: entry i in the REFERENCE's state-dict order (DeterministicDecoder: rnn.*, actions.mlp.*, gripper.mlp.*;
+ *                        the state embeddings of a use_state head are not listed): name (into name[name_len]), offset and numel in floats
+ *                        (offsets are multiples of 64 floats; the gaps are padding), decays = 1 for what the reference's apply_decay
+ *                        (train_calvin_post_strategy.py:471-482, exit_decay) decays among a head's tensors: Linear / LSTM weights, never a
+ *                        LayerNorm tensor or a bias.  i = -1: numel <- floats of the whole flat buffer (offset <- 0).
+ * deer_head_loss_grad    the taped window-mode forward of the head (DeterministicDecoder.forward, action_head.py:588-595, zero state, no
+ *                        dropout) from params on X [N][L][d] pooled rows, the loss gradient and the backward:
+ *                          loss_out[0] <- mean_rows( mean_6A Huber_1(pose - label) + w_bin mean_A BCEwithlogits(logit, grip01) ) over the
+ *                                         call's N L rows (train_utils.py:519-540; deer_exit_losses' arithmetic), NULL: not returned
+ *                          grad (+)= scale d loss / d params, flat like params (accumulate = 0: every entry is stored; padding untouched)
+ *                        pose [N L][6 A], grip01 [N L][A]; scale = exit weight x this call's share of a chunked batch (rows / all rows).
+ *                        Schedule: per LSTM layer one W_ih projection, L taped recurrent steps, [LayerNorm]; both MLP heads; then backward
+ *                        top-down: MLP (Linear dX / dW / db, LayerNorm, ReLU mask), per LSTM layer [LayerNorm backward], L recurrent
+ *                        launches t = L-1 .. 0, dW_ih = dG^T X_in, dW_hh = dG^T H_prev, db = colsum(dG), dX_in = dG W_ih.
+ *                        The model's LSTM state, control blocks, workspace and arena are not touched (no weights need to be loaded);
+ *                        scratch as deer_head_sequence (grown at the call that needs it - not capturable -, freed by deer_model_destroy).
+ *                        DEER_ERR_SHAPE before any launch: NULL pointer, N L <= 0 or > 2048 rows (the caller chunks whole sequences with
+ *                        accumulate = 1), multi_step_action outside 1..8, a head the model lacks, a use_state model (its head would need
+ *                        gradients for the state embeddings, which are not built; one line on stderr says so). */
+int deer_head_param_count(const deer_model* m, int head);
+int deer_head_param_entry(const deer_model* m, int head, int i, char* name, int name_len, long* offset, long* numel, int* decays);
+int deer_head_loss_grad(deer_model* m, int head, const float* params, const float* X, int N, int L, const float* pose, const float* grip01,
+                        float w_bin, float scale, float* grad, int accumulate, float* loss_out, void* stream);
 /* whole control step on ONE stream (vision batched): begin + vision + media K/V + trunk + heads */
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream);
 /* layers of the dynamic step: returns n and fills need_pseudo[i], is_exit[i], slot[i] for i < n (host only) */
