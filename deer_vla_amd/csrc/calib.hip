@@ -8,17 +8,16 @@
 //   deltas      of consecutive candidate layers (get_delta, value_net.py:105-117)
 // and is layer-major like csrc/head_seq.hip: at LSTM layer l a candidate row needs the history state (l, window, seq_id - 1) and its own
 // output of layer l - 1, so history rows and candidate rows share one W_ih projection GEMM per layer, and all candidate rows of a layer
-// are one recurrent launch.  The GEMMs / LayerNorms are head_seq.hip's kernels on more rows; this file adds
+// are one recurrent launch.  The GEMMs, LayerNorms and recurrent steps (deer_calib_lstm_step: the previous state read-only and per row
+// through an index) are head_seq.hip's kernels on more rows; this file holds
 //   calib_pool_layers_kernel   hidden[layer][row][d] of an env-batch engine -> P[frame][k][d], k over [0] + exit ids, pooled over the T
 //                              rows of a frame (AdaptiveMax/AvgPool1d, action_head.py:519-520; all T rows: no key mask reaches the head)
 //   calib_gather_kernel        P -> the history rows (the random layer's slot per (window, step)) and the candidate rows, + the
 //                              candidate row -> history row index
-//   calib_lstm_step_kernel     seq_lstm_step_kernel's arithmetic with separate c_prev / c_out and the previous state per row through an index
 //   calib_delta_kernel         actions [NL][rows][8 A] -> values [n_exit][rows]
 // No atomics, fixed summation order, every store a vector-memory store.
-#define DEER_BODIES_ONLY
-#include "head_seq.hip"
-#undef DEER_BODIES_ONLY
+#include "common.h"
+#include "../../include/deer_hip.h"
 
 namespace {
 
@@ -69,72 +68,6 @@ __global__ __launch_bounds__(256) void calib_gather_kernel(const float* __restri
   float4 v = float4{NAN, NAN, NAN, NAN};
   if (slot >= 0) v = *reinterpret_cast<const float4*>(P + ((b * W + t) * NL + slot) * d + i);
   *reinterpret_cast<float4*>(X + r * d + i) = v;
-}
-
-// seq_lstm_step_kernel (head_seq.hip) with the previous state read-only and per row: row m continues from row p = idx[m] (idx NULL:
-// p = m) of h_prev / c_prev, p < 0 (or h_prev NULL) = the zero state (zero_row: H zeros, the h operand of such a row).  Same tiling, same
-// k order, same wave-order sum of the partial tiles: a row's result does not depend on which other rows share the launch.
-template <int WK>
-__global__ __launch_bounds__(256) void calib_lstm_step_kernel(const float* __restrict__ pre, long ld_pre, const float* __restrict__ h_prev,
-                                                              long ld_h, const float* __restrict__ c_prev, long ld_c,
-                                                              const int* __restrict__ idx, const float* __restrict__ zero_row,
-                                                              const void* __restrict__ w_hh, const float* __restrict__ b_hh,
-                                                              float* __restrict__ c_out, long ld_co, float* __restrict__ h_out, long ld_out,
-                                                              int N, int H) {
-  __shared__ float part[4][4][SEQ_RT / 16][64][4];             // [wave][gate][row tile][lane][r]: 32 KB
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = lane & 15, g = lane >> 4;
-  const int u0 = blockIdx.x * 16, m0 = blockIdx.y * SEQ_RT;
-  f32x4 acc[4][SEQ_RT / 16];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < SEQ_RT / 16; ++j) acc[q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (h_prev != nullptr) {
-    const float* xp[SEQ_RT / 16];
-#pragma unroll
-    for (int j = 0; j < SEQ_RT / 16; ++j) {
-      const int m = min(m0 + j * 16 + c, N - 1);
-      const long p = idx != nullptr ? idx[m] : m;
-      xp[j] = p < 0 ? zero_row : h_prev + p * ld_h;
-    }
-#pragma unroll 2
-    for (int k0 = wave * 32; k0 < H; k0 += 128) {
-      const int k = k0 + g * 8;
-      const bool kval = k < H;
-      const int kc = kval ? k : 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const void* wp = seq_wrow<WK>(w_hh, (long)q * H + u0 + c, H, kc);
-#pragma unroll
-        for (int j = 0; j < SEQ_RT / 16; ++j) seq_frag_mac<WK>(wp, xp[j] + kc, kval, acc[q][j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < SEQ_RT / 16; ++j)
-      *reinterpret_cast<float4*>(&part[wave][q][j][lane][0]) = float4{acc[q][j][0], acc[q][j][1], acc[q][j][2], acc[q][j][3]};
-  __syncthreads();
-  for (int p = threadIdx.x; p < 16 * SEQ_RT; p += 256) {
-    const int ul = p & 15, rl = p >> 4;
-    const int m = m0 + rl, u = u0 + ul;
-    if (m >= N) continue;
-    const int j = rl >> 4, pl = ((ul >> 2) << 4) | (rl & 15), r = ul & 3;
-    float gq[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float s = ((part[0][q][j][pl][r] + part[1][q][j][pl][r]) + part[2][q][j][pl][r]) + part[3][q][j][pl][r];
-      gq[q] = (pre[(long)m * ld_pre + q * H + u] + s) + b_hh[q * H + u];
-    }
-    const long pr = idx != nullptr ? idx[m] : m;
-    const float cp = (c_prev != nullptr && pr >= 0) ? c_prev[pr * ld_c + u] : 0.f;
-    const float c2 = sigmoidf_(gq[1]) * cp + sigmoidf_(gq[0]) * tanhf(gq[2]);
-    const float h2 = sigmoidf_(gq[3]) * tanhf(c2);
-    if (c_out != nullptr) c_out[(long)m * ld_co + u] = c2;
-    h_out[(long)m * ld_out + u] = h2;
-  }
 }
 
 // get_delta (value_net.py:105-117) of consecutive candidate layers: values[e][r] = delta(actions[e][r], actions[e + 1][r]) over the NP
@@ -200,29 +133,6 @@ extern "C" int deer_calib_gather(const float* P, const int* rand_layers, const i
   if (R > 0x7fffffffL) return DEER_ERR_SHAPE;
   hipLaunchKernelGGL(calib_gather_kernel, dim3((unsigned)R, (d + 1023) / 1024), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), P, rand_layers,
                      tab, X, idx, bc, W, NL, d);
-  DEER_LAUNCH_CHECK();
-  return DEER_OK;
-}
-
-extern "C" int deer_calib_lstm_step(const float* pre, long ld_pre, const float* h_prev, long ld_h, const float* c_prev, long ld_c, const int* idx,
-                                    const float* zero_row, const void* w_hh, int w_kind, const float* b_hh, float* c_out, long ld_co,
-                                    float* h_out, long ld_out, int N, int H, void* stream) {
-  if (pre == nullptr || w_hh == nullptr || b_hh == nullptr || h_out == nullptr || N <= 0 || H <= 0 || (H & 15) ||
-      (h_prev != nullptr && ((ld_h & 7) || ld_h < H)) || (c_prev != nullptr && (h_prev == nullptr || ld_c < H)) ||
-      (idx != nullptr && h_prev != nullptr && zero_row == nullptr) || ld_pre < 4L * H || ld_out < H || (c_out != nullptr && ld_co < H) ||
-      w_kind < 0 || w_kind > 2 || (N + SEQ_RT - 1) / SEQ_RT > 65535)
-    return DEER_ERR_SHAPE;
-  dim3 grid(H / 16, (N + SEQ_RT - 1) / SEQ_RT);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (w_kind == SEQ_W_F32)
-    hipLaunchKernelGGL(calib_lstm_step_kernel<SEQ_W_F32>, grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, c_prev, ld_c, idx, zero_row, w_hh, b_hh,
-                       c_out, ld_co, h_out, ld_out, N, H);
-  else if (w_kind == SEQ_W_F16)
-    hipLaunchKernelGGL(calib_lstm_step_kernel<SEQ_W_F16>, grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, c_prev, ld_c, idx, zero_row, w_hh, b_hh,
-                       c_out, ld_co, h_out, ld_out, N, H);
-  else
-    hipLaunchKernelGGL(calib_lstm_step_kernel<SEQ_W_BF16>, grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, c_prev, ld_c, idx, zero_row, w_hh, b_hh,
-                       c_out, ld_co, h_out, ld_out, N, H);
   DEER_LAUNCH_CHECK();
   return DEER_OK;
 }

@@ -221,3 +221,6 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + expf(-
     hipError_t e_ = hipGetLastError();                        \
     if (e_ != hipSuccess) return DEER_ERR_LAUNCH;             \
   } while (0)
+
+// rows per workgroup of the window head's recurrent steps, forward (csrc/head_seq.hip) and backward (csrc/head_grad.hip)
+#define SEQ_RT 32

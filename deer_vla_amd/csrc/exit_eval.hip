@@ -6,7 +6,8 @@
 // 485-512), so the hidden states are pooled ONCE per (frame, layer) by deer_calib_pool_layers (csrc/calib.hip, any host list of layers - no
 // twin here) and everything below works on pooled [d] rows:
 //   window_gather_layers_kernel   X[s][(b, t)] = P[(b, t)][slot_of_layer[sel[s][b][t]]], all S selections in one launch
-//   exit_loss_rows_kernel         per (head, row): Huber(delta = 1) mean over the 6 A pose values, BCE-with-logits mean over the A logits
+//   exit_loss_rows_kernel         per (head, row): Huber(delta = 1) mean over the 6 A pose values, BCE-with-logits mean over the A logits;
+//                                 optionally their gradient (deer_head_grad_loss, the loss of exit-only fine-tuning: one head)
 //   exit_loss_reduce_kernel       per head: mean over the rows of num + w_bin bin, one workgroup, fixed summation order
 // No atomics, every sum has a fixed order (identical inputs give identical bits), every store is a vector-memory store.
 #include "common.h"
@@ -33,25 +34,34 @@ __global__ __launch_bounds__(256) void window_gather_layers_kernel(const float* 
 
 // One thread per (head h, row r).  num: F.huber_loss(pose, label, reduction='none').mean(-1) (train_utils.py:520; torch's form
 // |e| < 1 ? 0.5 e^2 : |e| - 0.5), bin: F.binary_cross_entropy_with_logits(logit, target, reduction='none').mean(-1) (:529) in the
-// overflow-safe form max(x, 0) - x y + log1p(exp(-|x|)); both summed in index order.
+// overflow-safe form max(x, 0) - x y + log1p(exp(-|x|)); both summed in index order.  dz (nullable; train_utils.py:519-543 backward):
+// dz[i] = d (scale mean_rows(num + w_bin bin)) / d [pre-tanh pose 6A | gripper logit A], g_pose / g_bin the two scale factors; the last A
+// slots of the 8 A wide row are zeroed.  torch's Huber backward: |e| < 1 ? e : sign(e).
 __global__ __launch_bounds__(256) void exit_loss_rows_kernel(const float* __restrict__ actions, const float* __restrict__ pose,
                                                              const float* __restrict__ grip01, float* __restrict__ num, float* __restrict__ bin,
-                                                             int Hn, long R, int A) {
+                                                             float* __restrict__ dz, int Hn, long R, int A, float g_pose, float g_bin) {
   const long i = (long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long)Hn * R) return;
   const long r = i % R;
   const float* a = actions + i * 8 * A;
   const float* p = pose + r * 6 * A;
   const float* g = grip01 + r * A;
+  float* d = dz != nullptr ? dz + i * 8 * A : nullptr;
   float sn = 0.f;
   for (int k = 0; k < 6 * A; ++k) {
-    const float e = fabsf(a[k] - p[k]);
+    const float df = a[k] - p[k];
+    const float e = fabsf(df);
     sn += e < 1.f ? 0.5f * e * e : e - 0.5f;
+    if (d != nullptr) d[k] = g_pose * (e < 1.f ? df : copysignf(1.f, df)) * (1.f - a[k] * a[k]);
   }
   float sb = 0.f;
   for (int k = 0; k < A; ++k) {
     const float x = a[7 * A + k];
     sb += (fmaxf(x, 0.f) - x * g[k]) + log1pf(expf(-fabsf(x)));
+    if (d != nullptr) {
+      d[6 * A + k] = g_bin * (a[6 * A + k] - g[k]);
+      d[7 * A + k] = 0.f;
+    }
   }
   num[i] = sn / (float)(6 * A);
   bin[i] = sb / (float)A;
@@ -101,9 +111,26 @@ extern "C" int deer_exit_losses(const float* actions, const float* pose, const f
     return DEER_ERR_SHAPE;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const long n = (long)Hn * R;
-  hipLaunchKernelGGL(exit_loss_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, actions, pose, grip01, num, bin, Hn, R, A);
+  hipLaunchKernelGGL(exit_loss_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, actions, pose, grip01, num, bin,
+                     static_cast<float*>(nullptr), Hn, R, A, 0.f, 0.f);
   DEER_LAUNCH_CHECK();
   hipLaunchKernelGGL(exit_loss_reduce_kernel, dim3(Hn), dim3(256), 0, st, num, bin, loss, R, w_bin);
+  DEER_LAUNCH_CHECK();
+  return DEER_OK;
+}
+
+// deer_exit_losses for one head, plus dz = d (scale loss) / d (pre-tanh pose, gripper logit) of every row
+extern "C" int deer_head_grad_loss(const float* actions, const float* pose, const float* grip01, long R, int A, float w_bin, float scale, float* dz,
+                                   float* num, float* bin, float* loss, void* stream) {
+  if (actions == nullptr || pose == nullptr || grip01 == nullptr || dz == nullptr || num == nullptr || bin == nullptr || loss == nullptr || R <= 0 ||
+      A <= 0 || A > 8 || R > 0x7fffffffL / (8 * A))
+    return DEER_ERR_SHAPE;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const float g_pose = scale / ((float)R * (float)(6 * A)), g_bin = scale * w_bin / ((float)R * (float)A);
+  hipLaunchKernelGGL(exit_loss_rows_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, actions, pose, grip01, num, bin, dz, 1, R, A, g_pose,
+                     g_bin);
+  DEER_LAUNCH_CHECK();
+  hipLaunchKernelGGL(exit_loss_reduce_kernel, dim3(1), dim3(256), 0, st, num, bin, loss, R, w_bin);
   DEER_LAUNCH_CHECK();
   return DEER_OK;
 }

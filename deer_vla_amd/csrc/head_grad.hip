@@ -3,9 +3,8 @@
 // csrc/head_seq.hip and csrc/exit_eval.hip do not already have.  The head is DeterministicDecoder in window mode (action_head.py:588-595)
 // on pooled rows X [N][L][d] from a zero state, no dropout, evaluated from a FLAT f32 parameter buffer (deer_head_param_entry).
 //
-//   forward (taped)   deer_head_seq_gemm (f32 weight rows: the exact-f32 MFMA) for every Linear; here the recurrent step that keeps the
-//                     activated gates, c_t and raw h_t, and a LayerNorm that keeps (mean, rstd) of every row
-//   loss gradient     d loss / d (pre-tanh pose, gripper logit) + the loss value in deer_exit_losses' arithmetic and summation order
+// The taped forward and the loss with its gradient are the kernels of those two files (deer_head_seq_gemm, deer_head_grad_lstm_step,
+// deer_head_grad_ln: csrc/head_seq.hip; deer_head_grad_loss: csrc/exit_eval.hip).  This file holds
 //   backward          a strided exact-f32 MFMA GEMM (dX = dY W, dW = dY^T X: either operand may be stored k-major), column sums
 //                     (db, LayerNorm d gamma / d beta), the ReLU mask, LayerNorm backward, one recurrent launch per time step
 //   deer_adamw_step   torch.optim.AdamW over flat (param, grad, m, v) buffers, decoupled decay per segment
@@ -13,143 +12,8 @@
 // vector-memory store; reads past a matrix edge are masked to zero and never stored.
 #include "common.h"
 #include "../../include/deer_hip.h"
-#define DEER_BODIES_ONLY
-#include "head_seq.hip"
-#undef DEER_BODIES_ONLY
 
 namespace {
-
-// ---- LayerNorm of rows that keeps the statistics: dst[m] = LN(src[m]) (ReLU when relu), stats[m] = (mean, rstd) ----------------------
-__global__ __launch_bounds__(256) void hg_ln_kernel(const float* src, long ld_src, float* dst, long ld_dst, const float* __restrict__ w,
-                                                    const float* __restrict__ b, float* __restrict__ stats, int M, int n, float eps, int relu) {
-  const int lane = threadIdx.x & 63;
-  const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (m >= M) return;
-  const float* s = src + m * ld_src;
-  float sum = 0.f;
-  for (int i = lane; i < n; i += 64) sum += s[i];
-  const float mean = wave_sum(sum) / n;
-  float var = 0.f;
-  for (int i = lane; i < n; i += 64) {
-    const float dv = s[i] - mean;
-    var += dv * dv;
-  }
-  const float rstd = rsqrtf(wave_sum(var) / n + eps);
-  if (lane == 0) {
-    stats[2 * m] = mean;
-    stats[2 * m + 1] = rstd;
-  }
-  for (int i = lane; i < n; i += 64) {
-    const float y = (s[i] - mean) * rstd * w[i] + b[i];
-    dst[m * ld_dst + i] = relu ? fmaxf(y, 0.f) : y;
-  }
-}
-
-// ---- taped LSTM time step (seq_lstm_step_kernel on f32 weight rows, csrc/head_seq.hip) ------------------------------------------------
-// gates [m][4H] holds pre = x W_ih^T + b_ih on entry and the ACTIVATED gates (s(i), s(f), tanh(g), s(o)) on return (each element read and
-// written by one thread); c_prev / h_prev NULL at t = 0 (zero state); c_out, h_out: this step's c_t and raw h_t.
-__global__ __launch_bounds__(256) void hg_lstm_step_kernel(float* gates, long ld_g, const float* __restrict__ h_prev, long ld_h,
-                                                           const float* __restrict__ w_hh, const float* __restrict__ b_hh,
-                                                           const float* __restrict__ c_prev, float* __restrict__ c_out, long ld_c,
-                                                           float* __restrict__ h_out, long ld_out, int N, int H) {
-  __shared__ float part[4][4][SEQ_RT / 16][64][4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = lane & 15, g = lane >> 4;
-  const int u0 = blockIdx.x * 16, m0 = blockIdx.y * SEQ_RT;
-  long xr[SEQ_RT / 16];
-#pragma unroll
-  for (int j = 0; j < SEQ_RT / 16; ++j) xr[j] = min(m0 + j * 16 + c, N - 1);
-  f32x4 acc[4][SEQ_RT / 16];
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < SEQ_RT / 16; ++j) acc[q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (h_prev != nullptr) {
-    for (int k0 = wave * 32; k0 < H; k0 += 128) {
-      const int k = k0 + g * 8;
-      const bool kval = k < H;
-      const int kc = kval ? k : 0;
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const void* wp = seq_wrow<SEQ_W_F32>(w_hh, (long)q * H + u0 + c, H, kc);
-#pragma unroll
-        for (int j = 0; j < SEQ_RT / 16; ++j) seq_frag_mac<SEQ_W_F32>(wp, h_prev + xr[j] * ld_h + kc, kval, acc[q][j]);
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < 4; ++q)
-#pragma unroll
-    for (int j = 0; j < SEQ_RT / 16; ++j)
-      *reinterpret_cast<float4*>(&part[wave][q][j][lane][0]) = float4{acc[q][j][0], acc[q][j][1], acc[q][j][2], acc[q][j][3]};
-  __syncthreads();
-  for (int p = threadIdx.x; p < 16 * SEQ_RT; p += 256) {
-    const int ul = p & 15, rl = p >> 4;
-    const int m = m0 + rl, u = u0 + ul;
-    if (m >= N) continue;
-    const int j = rl >> 4, pl = ((ul >> 2) << 4) | (rl & 15), r = ul & 3;
-    float gq[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const float s = ((part[0][q][j][pl][r] + part[1][q][j][pl][r]) + part[2][q][j][pl][r]) + part[3][q][j][pl][r];
-      gq[q] = (gates[(long)m * ld_g + q * H + u] + s) + b_hh[q * H + u];
-    }
-    const float cp = c_prev != nullptr ? c_prev[(long)m * ld_c + u] : 0.f;
-    const float gi = sigmoidf_(gq[0]), gf = sigmoidf_(gq[1]), gg = tanhf(gq[2]), go = sigmoidf_(gq[3]);
-    const float c2 = gf * cp + gi * gg;
-    gates[(long)m * ld_g + u] = gi;
-    gates[(long)m * ld_g + H + u] = gf;
-    gates[(long)m * ld_g + 2 * H + u] = gg;
-    gates[(long)m * ld_g + 3 * H + u] = go;
-    c_out[(long)m * ld_c + u] = c2;
-    h_out[(long)m * ld_out + u] = go * tanhf(c2);
-  }
-}
-
-// ---- loss rows + gradient (train_utils.py:519-543) -----------------------------------------------------------------------------------
-// One thread per row r: num / bin exactly as exit_loss_rows_kernel (csrc/exit_eval.hip); dz[r] = d (scale mean_rows(num + w_bin bin)) /
-// d [pre-tanh pose 6A | gripper logit A] (the last A slots of the 8 A wide row are zeroed).  torch's Huber backward: |e| < 1 ? e : sign(e).
-__global__ __launch_bounds__(256) void hg_loss_rows_kernel(const float* __restrict__ actions, const float* __restrict__ pose,
-                                                           const float* __restrict__ grip01, float* __restrict__ num, float* __restrict__ bin,
-                                                           float* __restrict__ dz, long R, int A, float g_pose, float g_bin) {
-  const long r = (long)blockIdx.x * 256 + threadIdx.x;
-  if (r >= R) return;
-  const float* a = actions + r * 8 * A;
-  const float* p = pose + r * 6 * A;
-  const float* g = grip01 + r * A;
-  float* d = dz + r * 8 * A;
-  float sn = 0.f;
-  for (int k = 0; k < 6 * A; ++k) {
-    const float df = a[k] - p[k];
-    const float e = fabsf(df);
-    sn += e < 1.f ? 0.5f * e * e : e - 0.5f;
-    d[k] = g_pose * (e < 1.f ? df : copysignf(1.f, df)) * (1.f - a[k] * a[k]);
-  }
-  float sb = 0.f;
-  for (int k = 0; k < A; ++k) {
-    const float x = a[7 * A + k];
-    sb += (fmaxf(x, 0.f) - x * g[k]) + log1pf(expf(-fabsf(x)));
-    d[6 * A + k] = g_bin * (a[6 * A + k] - g[k]);
-    d[7 * A + k] = 0.f;
-  }
-  num[r] = sn / (float)(6 * A);
-  bin[r] = sb / (float)A;
-}
-
-// exit_loss_reduce_kernel's order for one head: thread t sums rows t, t + 256, .., then a fixed tree
-__global__ __launch_bounds__(256) void hg_loss_reduce_kernel(const float* __restrict__ num, const float* __restrict__ bin, float* __restrict__ loss,
-                                                             long R, float w_bin) {
-  __shared__ float part[256];
-  float s = 0.f;
-  for (long r = threadIdx.x; r < R; r += 256) s += num[r] + w_bin * bin[r];
-  part[threadIdx.x] = s;
-  __syncthreads();
-  for (int w = 128; w > 0; w >>= 1) {
-    if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) loss[0] = part[0] / (float)R;
-}
 
 // ---- strided exact-f32 GEMM: C[m][n] (+)= sum_k opA(m, k) opB(n, k) --------------------------------------------------------------------
 // TA = 0: A stored [M][K] (row pitch lda), TA = 1: stored [K][M]; TB likewise for B ([N][K] is nn.Linear's layout).  The tile of
@@ -444,43 +308,6 @@ __global__ __launch_bounds__(256) void hg_adamw_kernel(float* __restrict__ p, co
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 }  // namespace
-
-extern "C" int deer_head_grad_ln(const float* src, long ld_src, float* dst, long ld_dst, const float* w, const float* b, float* stats, int M, int n,
-                                 float eps, int relu, void* stream) {
-  if (src == nullptr || dst == nullptr || w == nullptr || b == nullptr || stats == nullptr || M <= 0 || n <= 0 || ld_src < n || ld_dst < n)
-    return DEER_ERR_SHAPE;
-  hipLaunchKernelGGL(hg_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, ld_src, dst, ld_dst, w, b, stats, M,
-                     n, eps, relu);
-  DEER_LAUNCH_CHECK();
-  return DEER_OK;
-}
-
-extern "C" int deer_head_grad_lstm_step(float* gates, long ld_g, const float* h_prev, long ld_h, const float* w_hh, const float* b_hh,
-                                        const float* c_prev, float* c_out, long ld_c, float* h_out, long ld_out, int N, int H, void* stream) {
-  if (gates == nullptr || w_hh == nullptr || b_hh == nullptr || c_out == nullptr || h_out == nullptr || N <= 0 || H <= 0 || (H & 15) ||
-      (h_prev == nullptr) != (c_prev == nullptr) || (h_prev != nullptr && ((ld_h & 7) || ld_h < H)) || ld_g < 4L * H || ld_c < H || ld_out < H ||
-      (N + SEQ_RT - 1) / SEQ_RT > 65535)
-    return DEER_ERR_SHAPE;
-  hipLaunchKernelGGL(hg_lstm_step_kernel, dim3(H / 16, (N + SEQ_RT - 1) / SEQ_RT), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), gates, ld_g,
-                     h_prev, ld_h, w_hh, b_hh, c_prev, c_out, ld_c, h_out, ld_out, N, H);
-  DEER_LAUNCH_CHECK();
-  return DEER_OK;
-}
-
-extern "C" int deer_head_grad_loss(const float* actions, const float* pose, const float* grip01, long R, int A, float w_bin, float scale, float* dz,
-                                   float* num, float* bin, float* loss, void* stream) {
-  if (actions == nullptr || pose == nullptr || grip01 == nullptr || dz == nullptr || num == nullptr || bin == nullptr || loss == nullptr || R <= 0 ||
-      A <= 0 || A > 8 || R > 0x7fffffffL / (8 * A))
-    return DEER_ERR_SHAPE;
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const float g_pose = scale / ((float)R * (float)(6 * A)), g_bin = scale * w_bin / ((float)R * (float)A);
-  hipLaunchKernelGGL(hg_loss_rows_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, st, actions, pose, grip01, num, bin, dz, R, A, g_pose,
-                     g_bin);
-  DEER_LAUNCH_CHECK();
-  hipLaunchKernelGGL(hg_loss_reduce_kernel, dim3(1), dim3(256), 0, st, num, bin, loss, R, w_bin);
-  DEER_LAUNCH_CHECK();
-  return DEER_OK;
-}
 
 extern "C" int deer_head_grad_gemm(const float* A, long lda, int ta, const float* B, long ldb, int tb, float* C, long ldc, int M, int N, int K,
                                    int accumulate, void* stream) {

@@ -13,6 +13,9 @@
 // ~16 (bf16) / ~22 (fp16) significand bits of the activation; f32 weights use the exact-f32 MFMA
 // (v_mfma_f32_16x16x4_f32, as csrc/precise.hip).  No atomics: every sum has a fixed order, identical inputs give identical bits.
 // Every store is a vector-memory store; reads past a matrix edge are clamped to its last row / column and never stored.
+// The recurrent step and the LayerNorm serve three chains through nullable arguments: the sequence head (deer_head_seq_lstm_step,
+// deer_head_seq_ln), threshold calibration (deer_calib_lstm_step: previous state read-only and per row through an index) and the taped
+// forward of exit-only fine-tuning (deer_head_grad_lstm_step: activated gates kept; deer_head_grad_ln: (mean, rstd) kept).
 #include "common.h"
 #include "../../include/deer_hip.h"
 
@@ -190,28 +193,39 @@ __global__ __launch_bounds__(256) void seq_gemm_kernel(const float* __restrict__
 }
 
 // ---- one LSTM time step of one layer over N rows (torch.nn.LSTM gate order i, f, g, o) ------------------------------------------
-// gates = pre[m] + h_prev[m] W_hh^T + b_hh; c' = s(f) c + s(i) tanh(g); h' = s(o) tanh(c').  Workgroup = 16 hidden units x 32 rows;
-// its four waves split K = H (k-steps w, w + 4, ...), the partial tiles of the four gates meet in LDS and are summed in wave order.
-// c_state [N][H] is read and written in place (each element by one thread); h_out row m at h_out + m * ld_out.
-#define SEQ_RT 32
-template <int WK>
-__global__ __launch_bounds__(256) void seq_lstm_step_kernel(const float* __restrict__ pre, long ld_pre, const float* __restrict__ h_prev,
-                                                            long ld_h, const void* __restrict__ w_hh, const float* __restrict__ b_hh,
-                                                            float* __restrict__ c_state, float* __restrict__ h_out, long ld_out,
-                                                            float* __restrict__ h_n, float* __restrict__ c_n, int N, int H) {
+// gates = pre[m] + h_prev[p] W_hh^T + b_hh; c' = s(f) c_prev[p] + s(i) tanh(g); h' = s(o) tanh(c').  Row m continues from row p = idx[m]
+// (idx NULL: p = m) of h_prev / c_prev; p < 0 is the zero state (zero_row: H zeros, the h operand of such a row); h_prev NULL: no
+// recurrent term at all, c_prev NULL: c = 0.  Workgroup = 16 hidden units x SEQ_RT rows; its four waves split K = H (k-steps w, w + 4,
+// ...), the partial tiles of the four gates meet in LDS and are summed in wave order: a row's result does not depend on which other rows
+// share the launch.  Outputs: h_out row m at h_out + m * ld_out; optional c_out (pitch ld_co), dense h_n / c_n [N][H] and gates_out
+// (pitch ld_g): the activated gates s(i), s(f), tanh(g), s(o).  c_out may be c_prev (idx NULL) and gates_out may be pre: every element
+// is then read and written by the same thread, so those four pointers carry no __restrict__.  IDX / TAPE: idx / gates_out are in use
+// (compile-time, so the sequence head's form pays for neither).  A thread owns 16 SEQ_RT / 256 (unit, row) elements: it loads the inputs
+// of all of them before it stores any, so the loads of the second do not wait behind the stores of the first.
+template <int WK, bool IDX, bool TAPE>
+__global__ __launch_bounds__(256) void seq_lstm_step_kernel(const float* pre, long ld_pre, const float* __restrict__ h_prev, long ld_h,
+                                                            const float* c_prev, long ld_c, const int* __restrict__ idx,
+                                                            const float* __restrict__ zero_row, const void* __restrict__ w_hh,
+                                                            const float* __restrict__ b_hh, float* c_out, long ld_co,
+                                                            float* __restrict__ h_out, long ld_out, float* __restrict__ h_n,
+                                                            float* __restrict__ c_n, float* gates_out, long ld_g, int N, int H) {
   __shared__ float part[4][4][SEQ_RT / 16][64][4];             // [wave][gate][row tile][lane][r]: 32 KB
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int c = lane & 15, g = lane >> 4;
   const int u0 = blockIdx.x * 16, m0 = blockIdx.y * SEQ_RT;
-  long xr[SEQ_RT / 16];
-#pragma unroll
-  for (int j = 0; j < SEQ_RT / 16; ++j) xr[j] = min(m0 + j * 16 + c, N - 1);
   f32x4 acc[4][SEQ_RT / 16];
 #pragma unroll
   for (int q = 0; q < 4; ++q)
 #pragma unroll
     for (int j = 0; j < SEQ_RT / 16; ++j) acc[q][j] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (h_prev != nullptr) {
+    const float* xp[SEQ_RT / 16];
+#pragma unroll
+    for (int j = 0; j < SEQ_RT / 16; ++j) {
+      const int m = min(m0 + j * 16 + c, N - 1);
+      const long p = IDX ? idx[m] : m;
+      xp[j] = p < 0 ? zero_row : h_prev + p * ld_h;
+    }
 #pragma unroll 2
     for (int k0 = wave * 32; k0 < H; k0 += 128) {
       const int k = k0 + g * 8;
@@ -221,7 +235,7 @@ __global__ __launch_bounds__(256) void seq_lstm_step_kernel(const float* __restr
       for (int q = 0; q < 4; ++q) {
         const void* wp = seq_wrow<WK>(w_hh, (long)q * H + u0 + c, H, kc);
 #pragma unroll
-        for (int j = 0; j < SEQ_RT / 16; ++j) seq_frag_mac<WK>(wp, h_prev + xr[j] * ld_h + kc, kval, acc[q][j]);
+        for (int j = 0; j < SEQ_RT / 16; ++j) seq_frag_mac<WK>(wp, xp[j] + kc, kval, acc[q][j]);
       }
     }
   }
@@ -231,21 +245,39 @@ __global__ __launch_bounds__(256) void seq_lstm_step_kernel(const float* __restr
     for (int j = 0; j < SEQ_RT / 16; ++j)
       *reinterpret_cast<float4*>(&part[wave][q][j][lane][0]) = float4{acc[q][j][0], acc[q][j][1], acc[q][j][2], acc[q][j][3]};
   __syncthreads();
-  for (int p = threadIdx.x; p < 16 * SEQ_RT; p += 256) {
+  constexpr int EP = 16 * SEQ_RT / 256;
+  float gq[EP][4], cp[EP];
+#pragma unroll
+  for (int e = 0; e < EP; ++e) {
+    const int p = threadIdx.x + e * 256;
     const int ul = p & 15, rl = p >> 4;
     const int m = m0 + rl, u = u0 + ul;
     if (m >= N) continue;
     const int j = rl >> 4, pl = ((ul >> 2) << 4) | (rl & 15), r = ul & 3;
-    float gq[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
       const float s = ((part[0][q][j][pl][r] + part[1][q][j][pl][r]) + part[2][q][j][pl][r]) + part[3][q][j][pl][r];
-      gq[q] = (pre[(long)m * ld_pre + q * H + u] + s) + b_hh[q * H + u];
+      gq[e][q] = (pre[(long)m * ld_pre + q * H + u] + s) + b_hh[q * H + u];
     }
-    const float cp = c_state[(long)m * H + u];
-    const float c2 = sigmoidf_(gq[1]) * cp + sigmoidf_(gq[0]) * tanhf(gq[2]);
-    const float h2 = sigmoidf_(gq[3]) * tanhf(c2);
-    c_state[(long)m * H + u] = c2;
+    const long pr = IDX ? idx[m] : m;
+    cp[e] = (c_prev != nullptr && pr >= 0) ? c_prev[pr * ld_c + u] : 0.f;
+  }
+#pragma unroll
+  for (int e = 0; e < EP; ++e) {
+    const int p = threadIdx.x + e * 256;
+    const int m = m0 + (p >> 4), u = u0 + (p & 15);
+    if (m >= N) continue;
+    const float gi = sigmoidf_(gq[e][0]), gf = sigmoidf_(gq[e][1]), gg = tanhf(gq[e][2]), go = sigmoidf_(gq[e][3]);
+    const float c2 = gf * cp[e] + gi * gg;
+    const float h2 = go * tanhf(c2);
+    if constexpr (TAPE) {
+      float* go_row = gates_out + (long)m * ld_g;
+      go_row[u] = gi;
+      go_row[H + u] = gf;
+      go_row[2 * H + u] = gg;
+      go_row[3 * H + u] = go;
+    }
+    if (c_out != nullptr) c_out[(long)m * ld_co + u] = c2;
     h_out[(long)m * ld_out + u] = h2;
     if (h_n != nullptr) {
       h_n[(long)m * H + u] = h2;
@@ -254,10 +286,10 @@ __global__ __launch_bounds__(256) void seq_lstm_step_kernel(const float* __restr
   }
 }
 
-// ---- LayerNorm of rows (one wave per row), optional ReLU: dst[m] = LN(src[m]) ----------------------------------------------------
+// ---- LayerNorm of rows (one wave per row), optional ReLU: dst[m] = LN(src[m]); stats (nullable): stats[m] = (mean, rstd) ----------
 __global__ __launch_bounds__(256) void seq_ln_kernel(const float* src, long ld_src, float* dst, long ld_dst,
-                                                     const float* __restrict__ w, const float* __restrict__ b, int M, int n, float eps,
-                                                     int relu) {
+                                                     const float* __restrict__ w, const float* __restrict__ b, float* __restrict__ stats,
+                                                     int M, int n, float eps, int relu) {
   const int lane = threadIdx.x & 63;
   const long m = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (m >= M) return;
@@ -271,15 +303,49 @@ __global__ __launch_bounds__(256) void seq_ln_kernel(const float* src, long ld_s
     var += dv * dv;
   }
   const float rstd = rsqrtf(wave_sum(var) / n + eps);
+  if (stats != nullptr && lane == 0) {
+    stats[2 * m] = mean;
+    stats[2 * m + 1] = rstd;
+  }
   for (int i = lane; i < n; i += 64) {
     const float y = (s[i] - mean) * rstd * w[i] + b[i];
     dst[m * ld_dst + i] = relu ? fmaxf(y, 0.f) : y;
   }
 }
 
+// The one launch of seq_lstm_step_kernel: the three exported forms below are their own argument checks plus this call.
+static int seq_lstm_step_launch(const float* pre, long ld_pre, const float* h_prev, long ld_h, const float* c_prev, long ld_c, const int* idx,
+                                const float* zero_row, const void* w_hh, int w_kind, const float* b_hh, float* c_out, long ld_co, float* h_out,
+                                long ld_out, float* h_n, float* c_n, float* gates_out, long ld_g, int N, int H, void* stream) {
+  // in-place c is legal only where every thread reads the element it writes: not through an index.  Exact equality is what is tested;
+  // a c_out that merely overlaps c_prev is the caller's error.
+  // The tape exists on f32 rows without an index only.
+  const bool tape = gates_out != nullptr;
+  if (w_kind < 0 || w_kind > 2 || (N + SEQ_RT - 1) / SEQ_RT > 65535 || (idx != nullptr && c_out != nullptr && c_out == c_prev) ||
+      (tape && (w_kind != SEQ_W_F32 || idx != nullptr)))
+    return DEER_ERR_SHAPE;
+  dim3 grid(H / 16, (N + SEQ_RT - 1) / SEQ_RT);
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define SEQ_STEP_LAUNCH(WK, IDX, TAPE)                                                                                                       \
+  hipLaunchKernelGGL((seq_lstm_step_kernel<WK, IDX, TAPE>), grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, c_prev, ld_c, idx, zero_row, w_hh, b_hh, c_out, \
+                     ld_co, h_out, ld_out, h_n, c_n, gates_out, ld_g, N, H)
+#define SEQ_STEP_IDX(WK)                      \
+  do {                                        \
+    if (idx != nullptr) SEQ_STEP_LAUNCH(WK, true, false); \
+    else SEQ_STEP_LAUNCH(WK, false, false);   \
+  } while (0)
+  if (tape) SEQ_STEP_LAUNCH(SEQ_W_F32, false, true);
+  else if (w_kind == SEQ_W_F32) SEQ_STEP_IDX(SEQ_W_F32);
+  else if (w_kind == SEQ_W_F16) SEQ_STEP_IDX(SEQ_W_F16);
+  else SEQ_STEP_IDX(SEQ_W_BF16);
+#undef SEQ_STEP_IDX
+#undef SEQ_STEP_LAUNCH
+  DEER_LAUNCH_CHECK();
+  return DEER_OK;
+}
+
 }  // namespace
 
-#ifndef DEER_BODIES_ONLY   // csrc/calib.hip includes the fragment helpers and kernels above, not the entry points
 extern "C" int deer_head_seq_pool(const float* feats, const float* emb, float* X, int M, int T, int d, int avg, void* stream) {
   if (feats == nullptr || X == nullptr || M <= 0 || M > 65535 || T <= 0 || d <= 0) return DEER_ERR_SHAPE;
   hipLaunchKernelGGL(seq_pool_kernel, dim3((d + 255) / 256, M), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), feats, emb, X, T, d, avg);
@@ -311,32 +377,58 @@ extern "C" int deer_head_seq_gemm(const float* X, long ldx, const void* W, int w
   return DEER_OK;
 }
 
+// c_state [N][H] is read and written in place (each element by one thread).  Unlike the two forms below this one does not ask for
+// ld_h >= H: the rule is inherited as it was, and the refusal tests pin it.
 extern "C" int deer_head_seq_lstm_step(const float* pre, long ld_pre, const float* h_prev, long ld_h, const void* w_hh, int w_kind,
                                        const float* b_hh, float* c_state, float* h_out, long ld_out, float* h_n, float* c_n, int N, int H,
                                        void* stream) {
   if (pre == nullptr || w_hh == nullptr || b_hh == nullptr || c_state == nullptr || h_out == nullptr || N <= 0 || H <= 0 || (H & 15) ||
-      (h_prev != nullptr && (ld_h & 7)) || ld_pre < 4L * H || ld_out < H || (h_n == nullptr) != (c_n == nullptr) || w_kind < 0 || w_kind > 2 ||
-      (N + SEQ_RT - 1) / SEQ_RT > 65535)
+      (h_prev != nullptr && (ld_h & 7)) || ld_pre < 4L * H || ld_out < H || (h_n == nullptr) != (c_n == nullptr))
     return DEER_ERR_SHAPE;
-  dim3 grid(H / 16, (N + SEQ_RT - 1) / SEQ_RT);
-  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (w_kind == SEQ_W_F32)
-    hipLaunchKernelGGL(seq_lstm_step_kernel<SEQ_W_F32>, grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, w_hh, b_hh, c_state, h_out, ld_out, h_n, c_n, N, H);
-  else if (w_kind == SEQ_W_F16)
-    hipLaunchKernelGGL(seq_lstm_step_kernel<SEQ_W_F16>, grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, w_hh, b_hh, c_state, h_out, ld_out, h_n, c_n, N, H);
-  else
-    hipLaunchKernelGGL(seq_lstm_step_kernel<SEQ_W_BF16>, grid, dim3(256), 0, st, pre, ld_pre, h_prev, ld_h, w_hh, b_hh, c_state, h_out, ld_out, h_n, c_n, N, H);
-  DEER_LAUNCH_CHECK();
-  return DEER_OK;
+  return seq_lstm_step_launch(pre, ld_pre, h_prev, ld_h, c_state, H, nullptr, nullptr, w_hh, w_kind, b_hh, c_state, H, h_out, ld_out, h_n, c_n,
+                              nullptr, 0, N, H, stream);
+}
+
+// the previous state read-only and per row through an index (csrc/calib.hip: history and candidate rows)
+extern "C" int deer_calib_lstm_step(const float* pre, long ld_pre, const float* h_prev, long ld_h, const float* c_prev, long ld_c, const int* idx,
+                                    const float* zero_row, const void* w_hh, int w_kind, const float* b_hh, float* c_out, long ld_co,
+                                    float* h_out, long ld_out, int N, int H, void* stream) {
+  if (pre == nullptr || w_hh == nullptr || b_hh == nullptr || h_out == nullptr || N <= 0 || H <= 0 || (H & 15) ||
+      (h_prev != nullptr && ((ld_h & 7) || ld_h < H)) || (c_prev != nullptr && (h_prev == nullptr || ld_c < H)) ||
+      (idx != nullptr && h_prev != nullptr && zero_row == nullptr) || ld_pre < 4L * H || ld_out < H || (c_out != nullptr && ld_co < H))
+    return DEER_ERR_SHAPE;
+  return seq_lstm_step_launch(pre, ld_pre, h_prev, ld_h, c_prev, ld_c, idx, zero_row, w_hh, w_kind, b_hh, c_out, ld_co, h_out, ld_out, nullptr,
+                              nullptr, nullptr, 0, N, H, stream);
+}
+
+// the taped step of csrc/head_grad.hip on f32 weight rows: gates [m][4H] holds pre = x W_ih^T + b_ih on entry and the ACTIVATED gates on
+// return; c_prev / h_prev NULL at t = 0 (zero state); c_out, h_out: this step's c_t and raw h_t
+extern "C" int deer_head_grad_lstm_step(float* gates, long ld_g, const float* h_prev, long ld_h, const float* w_hh, const float* b_hh,
+                                        const float* c_prev, float* c_out, long ld_c, float* h_out, long ld_out, int N, int H, void* stream) {
+  if (gates == nullptr || w_hh == nullptr || b_hh == nullptr || c_out == nullptr || h_out == nullptr || N <= 0 || H <= 0 || (H & 15) ||
+      (h_prev == nullptr) != (c_prev == nullptr) || (h_prev != nullptr && ((ld_h & 7) || ld_h < H)) || ld_g < 4L * H || ld_c < H || ld_out < H)
+    return DEER_ERR_SHAPE;
+  return seq_lstm_step_launch(gates, ld_g, h_prev, ld_h, c_prev, ld_c, nullptr, nullptr, w_hh, SEQ_W_F32, b_hh, c_out, ld_c, h_out, ld_out, nullptr,
+                              nullptr, gates, ld_g, N, H, stream);
 }
 
 extern "C" int deer_head_seq_ln(const float* src, long ld_src, float* dst, long ld_dst, const float* w, const float* b, int M, int n, float eps,
                                 int relu, void* stream) {
   if (src == nullptr || dst == nullptr || w == nullptr || b == nullptr || M <= 0 || n <= 0 || ld_src < n || ld_dst < n)
     return DEER_ERR_SHAPE;
-  hipLaunchKernelGGL(seq_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, ld_src, dst, ld_dst, w, b, M, n,
-                     eps, relu);
+  hipLaunchKernelGGL(seq_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, ld_src, dst, ld_dst, w, b,
+                     static_cast<float*>(nullptr), M, n, eps, relu);
   DEER_LAUNCH_CHECK();
   return DEER_OK;
 }
-#endif  // DEER_BODIES_ONLY
+
+// deer_head_seq_ln that keeps the statistics of every row for the backward: stats[m] = (mean, rstd)
+extern "C" int deer_head_grad_ln(const float* src, long ld_src, float* dst, long ld_dst, const float* w, const float* b, float* stats, int M, int n,
+                                 float eps, int relu, void* stream) {
+  if (src == nullptr || dst == nullptr || w == nullptr || b == nullptr || stats == nullptr || M <= 0 || n <= 0 || ld_src < n || ld_dst < n)
+    return DEER_ERR_SHAPE;
+  hipLaunchKernelGGL(seq_ln_kernel, dim3((M + 3) / 4), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), src, ld_src, dst, ld_dst, w, b, stats, M,
+                     n, eps, relu);
+  DEER_LAUNCH_CHECK();
+  return DEER_OK;
+}

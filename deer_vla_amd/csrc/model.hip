@@ -1551,42 +1551,80 @@ struct ScratchTake {                // carves the scratch into float blocks, eac
   }
 };
 
+// One DeterministicDecoder's weights: its offset tables, the buffer they count from and the format of its weight rows.  w() / f() resolve
+// an offset to a device pointer (NULL: the head has no such tensor).
+struct HeadView {
+  const std::vector<LstmW>& lstm;
+  const std::vector<FcW>& fc;
+  size_t wa, ba, wg, bg;
+  const char* base;
+  size_t unit;                       // bytes per offset unit: 1 in the arena, sizeof(float) in a flat f32 parameter buffer
+  int wkind;
+  const void* w(size_t off) const { return off == SIZE_MAX ? nullptr : base + off * unit; }
+  const float* f(size_t off) const { return static_cast<const float*>(w(off)); }
+};
+// from the arena: head 0 = extra_exit (m->lstm / m->fc / m->wa ..), head k = the per-layer head m->lw[k - 1]
+HeadView head_view(const deer_model* m, int head) {
+  if (head == 0) return {m->lstm, m->fc, m->wa, m->ba, m->wg, m->bg, m->arena, 1, m->wkind};
+  const HeadW& h = m->lw[head - 1];
+  return {h.lstm, h.fc, h.wa, h.ba, h.wg, h.bg, m->arena, 1, m->wkind};
+}
+// from a flat f32 parameter buffer (exit-only fine-tuning)
+HeadView head_view(const HeadFlat& F, const float* params) {
+  return {F.lstm, F.fc, F.wa, F.ba, F.wg, F.bg, reinterpret_cast<const char*>(params), sizeof(float), 1};
+}
+
+// Row LayerNorm of the window head; stats (nullable) keeps (mean, rstd) of every row for a backward
+int seq_ln(const float* src, float* dst, const float* w, const float* b, float* stats, int rows, int n, int relu, void* stream) {
+  if (stats != nullptr) return deer_head_grad_ln(src, n, dst, n, w, b, stats, rows, n, kEps, relu, stream);
+  return deer_head_seq_ln(src, n, dst, n, w, b, rows, n, kEps, relu, stream);
+}
+
 // Input of LSTM layer l for `rows` rows, projected: layer 0 reads X [rows][d]; a higher layer reads the previous layer's outputs Y
-// [rows][H], LayerNorm'ed into X with that layer's parameters under lstm_layernorm.  PRE [rows][4H] <- input W_ih^T + b_ih.
-int seq_lstm_input(const deer_model* m, const std::vector<LstmW>& lstm_w, int l, float* X, const float* Y, float* PRE, int rows, void* stream) {
+// [rows][H], LayerNorm'ed into XN (statistics into `stats` when given) with that layer's parameters under lstm_layernorm.
+// PRE [rows][4H] <- input W_ih^T + b_ih.
+int seq_lstm_input(const deer_model* m, const HeadView& hv, int l, const float* X, const float* Y, float* XN, float* stats, float* PRE, int rows,
+                   void* stream) {
   const int d = m->d, H = m->H;
   const float* xin = X;
   int in_dim = d;
   if (l > 0) {
     in_dim = H;
-    if (m->c.lstm_layernorm) DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(lstm_w[l - 1].lnw), m->A<float>(lstm_w[l - 1].lnb), rows, H, kEps, 0, stream));
-    else xin = Y;
+    xin = Y;
+    if (m->c.lstm_layernorm) {
+      DEER_TRY(seq_ln(Y, XN, hv.f(hv.lstm[l - 1].lnw), hv.f(hv.lstm[l - 1].lnb), stats, rows, H, 0, stream));
+      xin = XN;
+    }
   }
-  DEER_TRY(deer_head_seq_gemm(xin, in_dim, m->A<void>(lstm_w[l].wih), m->wkind, m->A<float>(lstm_w[l].bih), PRE, 4L * H, rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+  DEER_TRY(deer_head_seq_gemm(xin, in_dim, hv.w(hv.lstm[l].wih), hv.wkind, hv.f(hv.lstm[l].bih), PRE, 4L * H, rows, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
   return DEER_OK;
 }
 
-// The two MLP heads (action_head.py:86-136) on mr rows x_rows (row pitch ld_x, H wide): hidden Linears with ReLU or LayerNorm through the
-// ping-pong buffers Z[head group], then the output Linears straight into act (row pitch ld_act): [pose 6A, tanh | gripper prob A | logit A]
-int seq_mlp_heads(const deer_model* m, const std::vector<FcW>& fc_w, size_t wa, size_t ba, size_t wg, size_t bg, const float* x_rows, long ld_x,
-                  int mr, float* Z[2][2], float* act, long ld_act, void* stream) {
+// The two MLP heads (action_head.py:86-136) on mr rows x_rows (row pitch ld_x, H wide): hidden Linears with ReLU or LayerNorm + ReLU, then
+// the output Linears straight into act (row pitch ld_act): [pose 6A, tanh | gripper prob A | logit A].  Per-layer destination tables
+// [head group][layer]: ZA the activations, ZP (nullable) the pre-LayerNorm rows (NULL entry: LayerNorm in place), ZS (nullable) the
+// LayerNorm statistics.
+static_assert(sizeof(deer_model::fc_dims) == 3 * sizeof(int), "the [2][3] tables of seq_mlp_heads hold one entry per hidden layer");
+int seq_mlp_heads(const deer_model* m, const HeadView& hv, const float* x_rows, long ld_x, int mr, float* const ZA[2][3], float* const ZP[2][3],
+                  float* const ZS[2][3], float* act, long ld_act, void* stream) {
   const deer_config& c = m->c;
-  const int A = std::max(1, c.multi_step_action), wk = m->wkind;
+  const int A = std::max(1, c.multi_step_action), wk = hv.wkind;
   for (int g = 0; g < 2; ++g) {
     const float* src = x_rows;
     long lds = ld_x;
     int kin = m->H;
     for (int fi = 0; fi < m->n_fc; ++fi) {
-      const FcW& F = fc_w[fi];
+      const FcW& F = hv.fc[fi];
       const int dim = m->fc_dims[fi];
-      float* z = Z[g][fi & 1];
-      DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(F.w[g]), wk, m->A<float>(F.b[g]), z, dim, mr, dim, kin,
+      float* z = ZA[g][fi];
+      float* zp = ZP != nullptr && ZP[g][fi] != nullptr ? ZP[g][fi] : z;
+      DEER_TRY(deer_head_seq_gemm(src, lds, hv.w(F.w[g]), wk, hv.f(F.b[g]), c.mlp_layernorm ? zp : z, dim, mr, dim, kin,
                                   c.mlp_layernorm ? DEER_SEQ_EPI_NONE : DEER_SEQ_EPI_RELU, stream));
-      if (c.mlp_layernorm) DEER_TRY(deer_head_seq_ln(z, dim, z, dim, m->A<float>(F.lnw[g]), m->A<float>(F.lnb[g]), mr, dim, kEps, 1, stream));
+      if (c.mlp_layernorm) DEER_TRY(seq_ln(zp, z, hv.f(F.lnw[g]), hv.f(F.lnb[g]), ZS != nullptr ? ZS[g][fi] : nullptr, mr, dim, 1, stream));
       src = z; lds = dim; kin = dim;
     }
-    if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wa), wk, m->A<float>(ba), act, ld_act, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
-    else DEER_TRY(deer_head_seq_gemm(src, lds, m->A<void>(wg), wk, m->A<float>(bg), act + 6 * A, ld_act, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
+    if (g == 0) DEER_TRY(deer_head_seq_gemm(src, lds, hv.w(hv.wa), wk, hv.f(hv.ba), act, ld_act, mr, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
+    else DEER_TRY(deer_head_seq_gemm(src, lds, hv.w(hv.wg), wk, hv.f(hv.bg), act + 6 * A, ld_act, mr, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
   }
   return DEER_OK;
 }
@@ -1916,10 +1954,7 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
     return DEER_ERR_SHAPE;
   // use_state: the state rows are required, and only extra_exit carries the state embedding (action_head.py:443-453)
   if ((bool)c.use_state != with_state || (with_state && (state == nullptr || head != 0))) return DEER_ERR_SHAPE;
-  const HeadW* hw = head > 0 ? &m->lw[head - 1] : nullptr;
-  const std::vector<LstmW>& lstm_w = hw ? hw->lstm : m->lstm;
-  const std::vector<FcW>& fc_w = hw ? hw->fc : m->fc;
-  const size_t wa = hw ? hw->wa : m->wa, ba = hw ? hw->ba : m->ba, wg = hw ? hw->wg : m->wg, bg = hw ? hw->bg : m->bg;
+  const HeadView hv = head_view(m, head);
   const int d = m->d, H = m->H, Lh = m->Lh, A = std::max(1, c.multi_step_action), wk = m->wkind;
   const int fc_max = m->n_fc > 0 ? m->fc_dims[0] : H;
   // chunk: whole sequences, at most kSeqRows rows (a longer sequence is a chunk of its own)
@@ -1941,7 +1976,8 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
   float* Y = take(n_y);
   float* CS = take(n_c);
   float* HZ = take(n_c);
-  float* Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
+  float* const Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
+  float* const ZA[2][3] = {{Z[0][0], Z[0][1], Z[0][0]}, {Z[1][0], Z[1][1], Z[1][0]}};    // layer fi writes Z[g][fi & 1]
   if (hipMemsetAsync(HZ, 0, (size_t)n_c * sizeof(float), st) != hipSuccess) return DEER_ERR_LAUNCH;
   const int out_rows_per = last ? 1 : L;
   for (int n0 = 0; n0 < N; n0 += Nc) {
@@ -1959,8 +1995,8 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
       return DEER_ERR_LAUNCH;
     // ---- the LSTM, layer by layer ----
     for (int l = 0; l < Lh; ++l) {
-      const LstmW& Lw = lstm_w[l];
-      DEER_TRY(seq_lstm_input(m, lstm_w, l, X, Y, PRE, (int)rows, stream));
+      const LstmW& Lw = hv.lstm[l];
+      DEER_TRY(seq_lstm_input(m, hv, l, X, Y, X, nullptr, PRE, (int)rows, stream));
       const long so = (long)l * N * H + (long)n0 * H;             // (L_lstm, N, H) state tensors
       if (c0 != nullptr) {
         if (hipMemcpyAsync(CS, c0 + so, (size_t)nc * H * sizeof(float), hipMemcpyDeviceToDevice, st) != hipSuccess) return DEER_ERR_LAUNCH;
@@ -1971,14 +2007,14 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
         const float* hp = t > 0 ? Y + (long)(t - 1) * H : (h0 != nullptr ? h0 + so : HZ);
         const long ldh = t > 0 ? (long)L * H : H;
         const bool fin = t == L - 1 && h_n != nullptr;
-        DEER_TRY(deer_head_seq_lstm_step(PRE + (long)t * 4 * H, (long)L * 4 * H, hp, ldh, m->A<void>(Lw.whh), wk, m->A<float>(Lw.bhh), CS,
+        DEER_TRY(deer_head_seq_lstm_step(PRE + (long)t * 4 * H, (long)L * 4 * H, hp, ldh, hv.w(Lw.whh), wk, hv.f(Lw.bhh), CS,
                                          Y + (long)t * H, (long)L * H, fin ? h_n + so : nullptr, fin ? c_n + so : nullptr, nc, H, stream));
       }
     }
     // ---- LSTM output x (LayerNorm'ed with lstm_layernorm), all steps or the last one (last_action, :596-597) ----
     const float* xo = Y;
     if (c.lstm_layernorm) {
-      DEER_TRY(deer_head_seq_ln(Y, H, X, H, m->A<float>(lstm_w.back().lnw), m->A<float>(lstm_w.back().lnb), (int)rows, H, kEps, 0, stream));
+      DEER_TRY(seq_ln(Y, X, hv.f(hv.lstm.back().lnw), hv.f(hv.lstm.back().lnb), nullptr, (int)rows, H, 0, stream));
       xo = X;
     }
     const float* x_rows = last ? xo + (long)(L - 1) * H : xo;
@@ -1989,7 +2025,7 @@ int deer_head_sequence_ex(deer_model* m, int head, const float* feats, int N, in
                          hipMemcpyDeviceToDevice, st) != hipSuccess)
       return DEER_ERR_LAUNCH;
     // ---- the two MLP heads (action_head.py:86-136), outputs [pose 6A | gripper prob A | logit A] per row ----
-    DEER_TRY(seq_mlp_heads(m, fc_w, wa, ba, wg, bg, x_rows, ld_x, mr, Z, actions + (long)n0 * out_rows_per * 8 * A, 8L * A, stream));
+    DEER_TRY(seq_mlp_heads(m, hv, x_rows, ld_x, mr, ZA, nullptr, nullptr, actions + (long)n0 * out_rows_per * 8 * A, 8L * A, stream));
   }
   return DEER_OK;
 }
@@ -2089,38 +2125,18 @@ int deer_head_loss_grad(deer_model* m, int head, const float* params, const floa
   auto Pp = [&](size_t off) { return off == SIZE_MAX ? nullptr : params + off; };
   auto Gp = [&](size_t off) { return off == SIZE_MAX ? nullptr : grad + off; };
 
-  // ---- taped forward: the LSTM, layer by layer ----
+  // ---- taped forward: the chain of deer_head_sequence on the kept buffers (LSTM layer by layer, then the two MLP heads) ----
+  const HeadView hv = head_view(F, params);
   for (int l = 0; l < Lh; ++l) {
-    const LstmW& Lw = F.lstm[l];
-    const float* xin = l == 0 ? X : XN[l - 1];
-    const int in_dim = l == 0 ? d : H;
-    DEER_TRY(deer_head_seq_gemm(xin, in_dim, Pp(Lw.wih), 1, Pp(Lw.bih), G[l], 4L * H, R, 4 * H, in_dim, DEER_SEQ_EPI_NONE, stream));
+    DEER_TRY(seq_lstm_input(m, hv, l, X, l > 0 ? Y[l - 1] : nullptr, l > 0 ? XN[l - 1] : nullptr, l > 0 ? ST[l - 1] : nullptr, G[l], R, stream));
     for (int t = 0; t < L; ++t)
-      DEER_TRY(deer_head_grad_lstm_step(G[l] + (long)t * 4 * H, (long)L * 4 * H, t > 0 ? Y[l] + (long)(t - 1) * H : nullptr, (long)L * H, Pp(Lw.whh),
-                                        Pp(Lw.bhh), t > 0 ? C[l] + (long)(t - 1) * H : nullptr, C[l] + (long)t * H, (long)L * H,
-                                        Y[l] + (long)t * H, (long)L * H, N, H, stream));
-    if (lln) DEER_TRY(deer_head_grad_ln(Y[l], H, XN[l], H, Pp(Lw.lnw), Pp(Lw.lnb), ST[l], R, H, kEps, 0, stream));
+      DEER_TRY(deer_head_grad_lstm_step(G[l] + (long)t * 4 * H, (long)L * 4 * H, t > 0 ? Y[l] + (long)(t - 1) * H : nullptr, (long)L * H,
+                                        hv.f(hv.lstm[l].whh), hv.f(hv.lstm[l].bhh), t > 0 ? C[l] + (long)(t - 1) * H : nullptr,
+                                        C[l] + (long)t * H, (long)L * H, Y[l] + (long)t * H, (long)L * H, N, H, stream));
   }
+  if (lln) DEER_TRY(seq_ln(Y[Lh - 1], XN[Lh - 1], hv.f(hv.lstm[Lh - 1].lnw), hv.f(hv.lstm[Lh - 1].lnb), ST[Lh - 1], R, H, 0, stream));
   const float* XO = XN[Lh - 1];
-  // ---- taped forward: the two MLP heads (action_head.py:86-136) ----
-  for (int g = 0; g < 2; ++g) {
-    const float* src = XO;
-    int kin = H;
-    for (int fi = 0; fi < n_fc; ++fi) {
-      const FcW& W = F.fc[fi];
-      const int dim = m->fc_dims[fi];
-      if (mln) {
-        DEER_TRY(deer_head_seq_gemm(src, kin, Pp(W.w[g]), 1, Pp(W.b[g]), ZP[g][fi], dim, R, dim, kin, DEER_SEQ_EPI_NONE, stream));
-        DEER_TRY(deer_head_grad_ln(ZP[g][fi], dim, ZA[g][fi], dim, Pp(W.lnw[g]), Pp(W.lnb[g]), ZS[g][fi], R, dim, kEps, 1, stream));
-      } else {
-        DEER_TRY(deer_head_seq_gemm(src, kin, Pp(W.w[g]), 1, Pp(W.b[g]), ZA[g][fi], dim, R, dim, kin, DEER_SEQ_EPI_RELU, stream));
-      }
-      src = ZA[g][fi];
-      kin = dim;
-    }
-    if (g == 0) DEER_TRY(deer_head_seq_gemm(src, kin, Pp(F.wa), 1, Pp(F.ba), OUT, 8L * A, R, 6 * A, kin, DEER_SEQ_EPI_TANH, stream));
-    else DEER_TRY(deer_head_seq_gemm(src, kin, Pp(F.wg), 1, Pp(F.bg), OUT + 6 * A, 8L * A, R, A, kin, DEER_SEQ_EPI_SIGMOID_LOGIT, stream));
-  }
+  DEER_TRY(seq_mlp_heads(m, hv, XO, H, R, ZA, ZP, ZS, OUT, 8L * A, stream));
   // ---- loss value and d loss / d (pre-tanh pose, logit) ----
   float* LOSS = loss_out != nullptr ? loss_out : DC;           // DC is free until the backward's first recurrent step
   DEER_TRY(deer_head_grad_loss(OUT, pose, grip01, R, A, w_bin, scale, DZ, NUM, BIN, LOSS, stream));
@@ -2221,6 +2237,7 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
   if (NL < 0) return DEER_ERR_SHAPE;
   for (int l = 0; l < c.n_layers; ++l) slot_of[l] = -1;
   for (int k = 0; k < NL; ++k) slot_of[lay[k]] = k;
+  const HeadView hv = head_view(m, 0);
   const int d = m->d, H = m->H, Lh = m->Lh, A = std::max(1, c.multi_step_action), wk = m->wkind;
   const int S = W - W / 2, L = W - 1;
   const int fc_max = m->n_fc > 0 ? m->fc_dims[0] : H;
@@ -2241,7 +2258,8 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
   float* Y = take(n_y);
   float* CS = take(n_c);
   float* HZ = take(H);
-  float* Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
+  float* const Z[2][2] = {{take(n_z), take(n_z)}, {take(n_z), take(n_z)}};    // [head group][ping-pong]
+  float* const ZA[2][3] = {{Z[0][0], Z[0][1], Z[0][0]}, {Z[1][0], Z[1][1], Z[1][0]}};    // layer fi writes Z[g][fi & 1]
   float* ACT = take(n_act);
   int* IDX = reinterpret_cast<int*>(take(Rc));
   if (hipMemsetAsync(HZ, 0, (size_t)H * sizeof(float), st) != hipSuccess) return DEER_ERR_LAUNCH;
@@ -2251,24 +2269,24 @@ int deer_calibrate_values(deer_model* m, const float* P, const int* rand_layers,
     const long rh = (long)nb * L, rc = (long)NL * nb * S, rows = rh + rc;
     DEER_TRY(deer_calib_gather(P + (long)b0 * W * NL * d, rand_layers + (long)b0 * W, slot_of, c.n_layers, X, IDX, nb, W, NL, d, stream));
     for (int l = 0; l < Lh; ++l) {
-      const LstmW& Lw = m->lstm[l];
-      DEER_TRY(seq_lstm_input(m, m->lstm, l, X, Y, PRE, (int)rows, stream));      // W_ih of this layer once for history and candidate rows
+      const LstmW& Lw = hv.lstm[l];
+      DEER_TRY(seq_lstm_input(m, hv, l, X, Y, X, nullptr, PRE, (int)rows, stream));      // W_ih of this layer once for history and candidate rows
       // history: step t of every window from its step t - 1, (h, c) of every step kept in Y / CS rows (b, t)
       for (int t = 0; t < L; ++t)
         DEER_TRY(deer_calib_lstm_step(PRE + (long)t * 4 * H, (long)L * 4 * H, t > 0 ? Y + (long)(t - 1) * H : nullptr, (long)L * H,
-                                      t > 0 ? CS + (long)(t - 1) * H : nullptr, (long)L * H, nullptr, nullptr, m->A<void>(Lw.whh), wk,
-                                      m->A<float>(Lw.bhh), CS + (long)t * H, (long)L * H, Y + (long)t * H, (long)L * H, nb, H, stream));
+                                      t > 0 ? CS + (long)(t - 1) * H : nullptr, (long)L * H, nullptr, nullptr, hv.w(Lw.whh), wk, hv.f(Lw.bhh),
+                                      CS + (long)t * H, (long)L * H, Y + (long)t * H, (long)L * H, nb, H, stream));
       // candidates: one step of every (layer, window, seq_id) row from the history state after step seq_id - 1
-      DEER_TRY(deer_calib_lstm_step(PRE + rh * 4 * H, 4L * H, Y, H, CS, H, IDX, HZ, m->A<void>(Lw.whh), wk, m->A<float>(Lw.bhh), nullptr, 0,
+      DEER_TRY(deer_calib_lstm_step(PRE + rh * 4 * H, 4L * H, Y, H, CS, H, IDX, HZ, hv.w(Lw.whh), wk, hv.f(Lw.bhh), nullptr, 0,
                                     Y + rh * H, H, (int)rc, H, stream));
     }
     // ---- the candidates' LSTM output (LayerNorm'ed with lstm_layernorm) -> the two MLP heads (action_head.py:86-136) ----
     const float* xo = Y + rh * H;
     if (c.lstm_layernorm) {
-      DEER_TRY(deer_head_seq_ln(Y + rh * H, H, X, H, m->A<float>(m->lstm.back().lnw), m->A<float>(m->lstm.back().lnb), (int)rc, H, kEps, 0, stream));
+      DEER_TRY(seq_ln(Y + rh * H, X, hv.f(hv.lstm.back().lnw), hv.f(hv.lstm.back().lnb), nullptr, (int)rc, H, 0, stream));
       xo = X;
     }
-    DEER_TRY(seq_mlp_heads(m, m->fc, m->wa, m->ba, m->wg, m->bg, xo, H, (int)rc, Z, ACT, 8L * A, stream));
+    DEER_TRY(seq_mlp_heads(m, hv, xo, H, (int)rc, ZA, nullptr, nullptr, ACT, 8L * A, stream));
     // ---- deltas of consecutive candidate layers over the 6 A pose values, window-major columns b0 S .. ----
     DEER_TRY(deer_calib_delta(ACT, 8L * A, NL, nb * S, 6 * A, threshold_type, values + (long)b0 * S, n_val, stream));
     if (actions != nullptr &&

@@ -417,9 +417,9 @@ int deer_head_seq_ln(const float* src, long ld_src, float* dst, long ld_dst, con
  *                           t < W - 1 (the history, flamingo_mpt.py:486-490), then X[bc (W - 1) + (k, b, s)] = P[b][W/2 - 1 + s][k] for
  *                           s < W - W/2 (the candidates, value_net.py:139-153), and idx[(k, b, s)] = history row (b, W/2 - 2 + s) or -1.
  *                           rand_layers: DEVICE int32 [bc][W]; slot_of_layer: HOST int[n_layers] (-1: no slot -> NaN row).
- * deer_calib_lstm_step      deer_head_seq_lstm_step with a read-only previous state: row m continues from row idx[m] (idx NULL: m) of
- *                           h_prev / c_prev (row strides ld_h / ld_c); a negative index or h_prev NULL = the zero state (zero_row: H zeros).
- *                           c to c_out (or dropped when NULL), h to h_out.
+ * deer_calib_lstm_step      launches the sequence head's step kernel (deer_head_seq_lstm_step's, csrc/head_seq.hip) with a read-only previous
+ *                           state: row m continues from row idx[m] (idx NULL: m) of h_prev / c_prev (row strides ld_h / ld_c); a negative
+ *                           index or h_prev NULL = the zero state (zero_row: H zeros).  c to c_out (or dropped when NULL), h to h_out.
  * deer_calib_delta          values[e][r] = get_delta(actions[e][r], actions[e + 1][r]) (value_net.py:105-117) over the first NP values of
  *                           each action row; actions [NL][rows][ld_act], values [NL - 1][ld_val]; thr_type 0 L2, 1 mean, 2 max, 3 cosine. */
 #define DEER_CALIB_MAX_NL 17
@@ -456,13 +456,14 @@ int deer_exit_losses(const float* actions, const float* pose, const float* grip0
  * (only_train_head / no_backbone_grad, robot_flamingo/train/train_utils.py:487-543) and its optimizer (train_calvin_post_strategy.py:535) ----
  * Pieces that deer_head_loss_grad (deer_model.h) chains with deer_head_seq_gemm on f32 weight rows.  f32 arithmetic, fixed summation
  * orders, no atomics (two runs give identical bits); no dropout.
- * deer_head_grad_ln            deer_head_seq_ln (LayerNormLSTM action_head.py:44-53, MLP LayerNorm :97-103) that also keeps stats [M][2] =
- *                              (mean, rstd) of every row for the backward
- * deer_head_grad_lstm_step     deer_head_seq_lstm_step (one nn.LSTM step over N rows, gate order i, f, g, o) on f32 W_hh [4H][H] with a tape:
+ * deer_head_grad_ln            launches the sequence head's LayerNorm kernel (deer_head_seq_ln's, csrc/head_seq.hip: LayerNormLSTM
+ *                              action_head.py:44-53, MLP LayerNorm :97-103) and also keeps stats [M][2] = (mean, rstd) of every row for the backward
+ * deer_head_grad_lstm_step     launches the sequence head's step kernel (deer_head_seq_lstm_step's: one nn.LSTM step over N rows, gate order
+ *                              i, f, g, o) on f32 W_hh [4H][H] with a tape:
  *                              gates [N rows, pitch ld_g][4H] holds x W_ih^T + b_ih on entry and the ACTIVATED gates on return; c_out / h_out
  *                              receive c_t and the raw h_t; h_prev / c_prev both NULL at t = 0 (zero state).  H % 16 == 0.
  * deer_head_grad_loss          loss = mean_rows( mean_6A Huber_1(pose - label) + w_bin mean_A BCEwithlogits(logit, target) ) of one head
- *                              (train_utils.py:519-540) in deer_exit_losses' arithmetic and order (num, bin [R], loss [1]), and
+ *                              (train_utils.py:519-540): launches deer_exit_losses' two kernels (csrc/exit_eval.hip) for one head (num, bin [R], loss [1]), with
  *                              dz [R][8 A] = d (scale loss) / d [pre-tanh pose 6 A | gripper logit A | 0 A] (autograd of :519-543; scale =
  *                              exit weight x accumulation share).  actions [R][8 A] = [pose 6 A | prob A | logit A].
  * deer_head_grad_gemm          C[M][N] (+)= sum_k opA(m, k) opB(n, k), exact-f32 MFMA (v_mfma_f32_16x16x4_f32): ta / tb = 0 operand stored

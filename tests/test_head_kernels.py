@@ -894,3 +894,105 @@ def test_head_seq_pool(lib):
                     assert torch.equal(X.cpu(), feats[:, 0] if e is None else feats[:, 0] + e)
                 else:
                     _check_pool(X, feats, avg, add=e)
+
+
+# ================================================================================================ 8. one step / one loss kernel, three doors
+@pytest.mark.parametrize("wk", WKINDS)
+@pytest.mark.parametrize("H", [16, 48, 160])
+@pytest.mark.parametrize("N", [1, 33])
+def test_lstm_step_entry_points_same_bits(lib, wk, N, H):
+    """deer_head_seq_lstm_step (c in place, h_n / c_n), deer_calib_lstm_step (idx NULL with its own c_out; an identity idx) and, on f32
+    rows, deer_head_grad_lstm_step launch one kernel: equal h and c bit for bit, from a given state and from the zero state (NULL h_prev /
+    c_prev; the in-place form has no NULL for c and gets zeros).  N = 1 a lone row, 33 a ragged second 32-row tile; H = 16 / 48 leave
+    k-slices of a wave past H, 160 gives wave 0 a second k-iteration.  The taped gates reproduce c = gf c_prev + gi gg: two products and a
+    sum, each rounded once (2^-24 of its own magnitude) or fused, so |c - c64| <= 4 x 2^-24 (|gf c_prev| + |gi gg|) - relative to the
+    terms, as every gate of this module is, since the sum itself may cancel - and h = go tanh(c).  Every output is pitched and starts as NaN:
+    padding stays NaN."""
+    ld_pre, ld_h, ld_c, ld_out = 4 * H + 8, H + 8, H + 4, H + 12
+    pre = rnd(N, 4 * H, seed=11)
+    whh, _ = wq(rnd(4 * H, H, seed=14, scale=H ** -0.5), wk)
+    bhh_d = cu(rnd(4 * H, seed=15, scale=0.1))
+    pre_d = nanbuf(N, ld_pre)
+    pre_d[:, :4 * H] = cu(pre)
+    idx = torch.arange(N, dtype=torch.int32, device="cuda")
+    zero_row = torch.zeros(H, device="cuda")
+    for given in (True, False):
+        hp = nanbuf(N, ld_h)
+        hp[:, :H] = cu(rnd(N, H, seed=12, scale=0.5))
+        cp = nanbuf(N, ld_c)
+        cp[:, :H] = cu(rnd(N, H, seed=13, scale=0.5))
+        hp_p, cp_p = (abi.ptr(hp), abi.ptr(cp)) if given else (None, None)
+        # the sequence head's form
+        c_seq = cp[:, :H].clone() if given else torch.zeros(N, H, device="cuda")
+        h_seq, hn, cn = nanbuf(N, ld_out), nanbuf(N, H), nanbuf(N, H)
+        abi.check(lib.deer_head_seq_lstm_step(abi.ptr(pre_d), ld_pre, hp_p, ld_h, abi.ptr(whh), wk, abi.ptr(bhh_d), abi.ptr(c_seq), abi.ptr(h_seq),
+                                              ld_out, abi.ptr(hn), abi.ptr(cn), N, H, st()), "seq_lstm_step")
+        outs = []
+        # calibration's form: idx NULL, then the identity index
+        for ix in (None, idx):
+            c_o, h_o = nanbuf(N, ld_c), nanbuf(N, ld_out)
+            abi.check(lib.deer_calib_lstm_step(abi.ptr(pre_d), ld_pre, hp_p, ld_h, cp_p, ld_c, abi.ptr(ix), abi.ptr(zero_row), abi.ptr(whh), wk,
+                                               abi.ptr(bhh_d), abi.ptr(c_o), ld_c, abi.ptr(h_o), ld_out, N, H, st()), "calib_lstm_step")
+            outs.append(("calib idx " + ("NULL" if ix is None else "identity"), h_o, c_o))
+        gates = None
+        if wk == 1:                                          # the tape's form: f32 rows only
+            gates, c_o, h_o = pre_d.clone(), nanbuf(N, ld_c), nanbuf(N, ld_out)
+            abi.check(lib.deer_head_grad_lstm_step(abi.ptr(gates), ld_pre, hp_p, ld_h, abi.ptr(whh), abi.ptr(bhh_d), cp_p, abi.ptr(c_o), ld_c,
+                                                   abi.ptr(h_o), ld_out, N, H, st()), "head_grad_lstm_step")
+            outs.append(("tape", h_o, c_o))
+        sync()
+        assert bool(torch.isfinite(h_seq[:, :H]).all()) and bool(torch.isfinite(c_seq).all())
+        assert bool(torch.isnan(h_seq[:, H:]).all())
+        assert torch.equal(hn, h_seq[:, :H]) and torch.equal(cn, c_seq)
+        for what, h_o, c_o in outs:
+            assert torch.equal(h_o[:, :H], h_seq[:, :H]), f"{what}: h (state given: {given})"
+            assert torch.equal(c_o[:, :H], c_seq), f"{what}: c (state given: {given})"
+            assert bool(torch.isnan(h_o[:, H:]).all()) and bool(torch.isnan(c_o[:, H:]).all()), f"{what}: padding written"
+        if gates is not None:
+            assert bool(torch.isnan(gates[:, 4 * H:]).all())
+            gi, gf, gg, go = (gates[:, q * H:(q + 1) * H].double() for q in range(4))
+            c_prev = cp[:, :H].double() if given else torch.zeros(N, H, dtype=torch.float64, device="cuda")
+            t1, t2 = gf * c_prev, gi * gg
+            r = float(((c_seq.double() - (t1 + t2)).abs() / (t1.abs() + t2.abs())).max())
+            assert r <= 4 * 2.0 ** -24, f"taped gates vs c: {r:.3g}"
+            # the fourth slot: h = go tanh(c), one f32 tanh of a value <= 1 (2^-22, as in test_head_seq_lstm_step) and one product
+            rh = float(((h_seq[:, :H].double() - go * torch.tanh(c_seq.double())).abs() / go).max())
+            assert rh <= 2.0 ** -22 + 2.0 ** -24, f"taped gates vs h: {rh:.3g}"
+
+
+@pytest.mark.parametrize("R", [1, 257, 600])
+@pytest.mark.parametrize("A", [1, 2])
+def test_head_grad_loss_equals_exit_losses(lib, A, R):
+    """deer_head_grad_loss and deer_exit_losses with one head launch the same two kernels: num, bin and loss bit for bit.  R = 257 / 600: the
+    reduce's strided row loop (256 threads) with a ragged tail.  Pose errors a - label are exact in f32 and lie on both sides of the Huber
+    knee |e| = 1 (1 -+ 2^-20), at it and well away from it.  dz starts as NaN: all of it is written, its last A slots per row are zero, and
+    the rest is scale / R times [Huber'(e) (1 - a^2) / 6A | w_bin (prob - target) / A] in float64 within 8 x 2^-24 of each value: the f32
+    factor (two roundings), 1 - a^2 or prob - target (at most two; a^2 is exact for these a) and two products."""
+    errs = torch.tensor([0.25, -0.75, 1.0, -1.0, 1 + 2.0 ** -20, 1 - 2.0 ** -20, -(1 + 2.0 ** -20), -(1 - 2.0 ** -20), 1.5, -2.0, 0.0],
+                        dtype=torch.float64)
+    g = torch.Generator().manual_seed(100 * A + R)
+    act = torch.randn(R, 8 * A, generator=g, dtype=torch.float64)
+    act[:, :6 * A] = torch.randint(-8, 8, (R, 6 * A), generator=g).double() / 8        # multiples of 1/8: a - e and a - (a - e) are exact
+    e = errs[torch.randint(0, len(errs), (R, 6 * A), generator=g)]
+    e[0, 0] = 1.0
+    pose = (act[:, :6 * A] - e).float()
+    act = act.float()
+    assert torch.equal((act[:, :6 * A].double() - pose.double()), e)
+    grip = torch.randint(0, 2, (R, A), generator=g).float()
+    act_d, pose_d, grip_d = cu(act), cu(pose), cu(grip)
+    w_bin, scale = 0.01, 0.5
+    num_e, bin_e, loss_e = nanbuf(R), nanbuf(R), nanbuf(1)
+    abi.check(lib.deer_exit_losses(abi.ptr(act_d), abi.ptr(pose_d), abi.ptr(grip_d), 1, R, A, w_bin, abi.ptr(num_e), abi.ptr(bin_e), abi.ptr(loss_e),
+                                   st()), "exit_losses")
+    dz, num_g, bin_g, loss_g = nanbuf(R, 8 * A), nanbuf(R), nanbuf(R), nanbuf(1)
+    abi.check(lib.deer_head_grad_loss(abi.ptr(act_d), abi.ptr(pose_d), abi.ptr(grip_d), R, A, w_bin, scale, abi.ptr(dz), abi.ptr(num_g),
+                                      abi.ptr(bin_g), abi.ptr(loss_g), st()), "head_grad_loss")
+    sync()
+    assert bool(torch.isfinite(loss_e).all())
+    assert torch.equal(num_g, num_e) and torch.equal(bin_g, bin_e) and torch.equal(loss_g, loss_e)
+    assert bool(torch.isfinite(dz[:, :7 * A]).all()) and bool((dz[:, 7 * A:] == 0).all())
+    a64, wb = act.double(), float(np.float32(w_bin))
+    ref = torch.cat([scale / (R * 6 * A) * torch.where(e.abs() < 1, e, torch.sign(e)) * (1 - a64[:, :6 * A] ** 2),
+                     scale * wb / (R * A) * (a64[:, 6 * A:7 * A] - grip.double())], 1)
+    err = (dz[:, :7 * A].double().cpu() - ref).abs()
+    assert bool((err <= 8 * 2.0 ** -24 * ref.abs()).all()), float((err / ref.abs().clamp_min(1e-300)).max())
