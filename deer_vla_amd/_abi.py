@@ -142,6 +142,7 @@ SIGNATURES = {
     "deer_model_layerwise_head": [P, I],
     "deer_head_eval_layerwise": [P, I, I, I, I, P],
     "deer_step_enqueue": [P, I, I, I, I, P, P],
+    "deer_step_piece": [P, I, I, I, I, P],
     "deer_dynamic_plan": [P, P, P, P, I],
     # window mode of the head (csrc/head_seq.hip, include/deer_model.h deer_head_sequence)
     "deer_head_seq_pool": [P, P, P, I, I, I, I, P],
@@ -204,6 +205,7 @@ A_BF16, A_SLABS_GELU, A_SLABS, A_F32 = 0, 1, 2, 3
 X_RAW, X_POOL_MAX, X_POOL_AVG, X_LN = 0, 1, 2, 3
 PRO_RAW, PRO_LN, PRO_GROUP_LN_RELU, PRO_GROUP_RELU = 0, 1, 2, 3
 KIND_PSEUDO, KIND_CHECK, KIND_COMMIT = 0, 1, 2
+PIECE_MAIN, PIECE_HEADS, PIECE_STATIC = 0, 1, 2   # deer_step_piece (include/deer_model.h)
 SEQ_LAST_ACTION, SEQ_STATE = 1, 2                 # deer_head_sequence flags
 THR_TYPES = {"L2": 0, "mean": 1, "max": 2, "cosine": 3}
 

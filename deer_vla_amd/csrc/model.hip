@@ -165,6 +165,10 @@ int pick_split(long M, long N, long K, int target_blocks = 320, int max_split = 
   return S;
 }
 
+// One layer of the dynamic step (mosaic_gpt_3b.py:397-443, value_net.py:122-125): the pseudo-action evaluation and / or the exit check
+// that read its hidden state, and for env batches with compaction whether the layer gathers the surviving rows and which row map it uses
+struct PlanRow { int need_pseudo, is_exit, slot, compaction, parity; };
+
 }  // namespace
 
 struct ProfRec { std::string name; hipEvent_t e0, e1; double flops, bytes; };
@@ -215,6 +219,7 @@ struct deer_model {
   std::vector<int> exit_ids;
   int ctl_max_layer = 0, thr_type = 0, leq = 1;
   int cfg_max_layer = 0;            // the cap deer_model_configure_exit derived (ctl_max_layer while no per-environment table is active)
+  std::vector<PlanRow> plan;        // the dynamic step's layers 0 .. ctl_max_layer (set_max_layer)
   size_t env_exit = SIZE_MAX;       // per-environment operating points (common.h ENV_EXIT_*): threshold row + layer cap of every environment
   bool env_exit_on = false;         // deer_model_set_env_exit*: exit checks read env_exit; ctl_max_layer = the largest cap
   size_t ghh = 0;
@@ -785,7 +790,7 @@ int scatter_media(deer_model* m, const VisionWS& ws, void* st) {
   return DEER_OK;
 }
 
-int perceiver(deer_model* m, const VisionWS& ws, void* st) {
+int perceiver_b16(deer_model* m, const VisionWS& ws, void* st) {
   const deer_config& c = m->c;
   const PercSet& PS = m->ps[ws.cam];
   void* out_bf = ws.out_bf != SIZE_MAX ? m->Wk<void>(ws.out_bf) : m->Wk<void>(ws.vis_x);
@@ -846,7 +851,7 @@ int perceiver(deer_model* m, const VisionWS& ws, void* st) {
   return scatter_media(m, ws, st);
 }
 
-int vit_blocks(deer_model* m, const VisionWS& ws, int lo, int hi, void* st) {
+int vit_blocks_b16(deer_model* m, const VisionWS& ws, int lo, int hi, void* st) {
   const deer_config& c = m->c;
   const int W = m->W, tok = m->tok, H = c.vit_heads, N = ws.n;
   const long R = (long)N * tok;
@@ -924,7 +929,7 @@ int perceiver_f32(deer_model* m, const VisionWS& ws, void* st) {
   void* out_bf = ws.out_bf != SIZE_MAX ? m->Wk<void>(ws.out_bf) : m->Wk<void>(ws.vis_x);
   float* out_f32 = ws.out_f32 != SIZE_MAX ? m->Wk<float>(ws.out_f32) : m->Wk<float>(ws.vis_x_f32);
   const int P = m->P, W = m->W, tok = m->tok, nl = m->nl, inner = m->p_inner, Lp = m->Lp;
-  const int NF = ws.n, N = m->fuse_pre ? ws.n / 2 : ws.n, PM = m->fuse_pre ? 2 * P : P;      // pre fusion: see perceiver()
+  const int NF = ws.n, N = m->fuse_pre ? ws.n / 2 : ws.n, PM = m->fuse_pre ? 2 * P : P;      // pre fusion: see perceiver_b16()
   const long NL = (long)N * nl, NP = (long)NF * P, ffw = (long)c.perc_ff_mult * W;
   {
     Bracket b(m, "deer_broadcast_rows", 0, 0, st);
@@ -968,6 +973,13 @@ int perceiver_f32(deer_model* m, const VisionWS& ws, void* st) {
   }
   return scatter_media(m, ws, st);
 }
+
+// the tower in the model's arithmetic
+int vit_blocks(deer_model* m, const VisionWS& ws, int lo, int hi, void* st) {
+  return m->c.precision ? vit_blocks_f32(m, ws, lo, hi, st) : vit_blocks_b16(m, ws, lo, hi, st);
+}
+
+int perceiver(deer_model* m, const VisionWS& ws, void* st) { return m->c.precision ? perceiver_f32(m, ws, st) : perceiver_b16(m, ws, st); }
 
 int media_kv_f32(deer_model* m, void* st) {
   if (!m->n_xattn) return DEER_OK;
@@ -1033,10 +1045,30 @@ bool compact_on(const deer_model* m) { return m->compact && m->B > 1 && !m->c.pr
 // ... on the hi/lo-plane path of BOTH halves of a layer (every K a multiple of 64)
 bool compact_active(const deer_model* m, int R) { return compact_on(m) && block_hl(m, R) && ((((long)m->c.xattn_ff_mult * m->d) & 63) == 0); }
 
-struct PlanRow { int need_pseudo, is_exit, slot; };
-std::vector<PlanRow> dynamic_plan(const deer_model* m);
-bool is_compaction_layer(const deer_model* m, int layer);
-int cmap_parity(const deer_model* m, int layer);
+// The dynamic plan changes with the exits and the cap only: this sets the cap and rebuilds the rows.  Compaction layers: two layers
+// after every exit check (its verdict is complete before that layer starts); parity: which of the two row maps the layer uses.
+void set_max_layer(deer_model* m, int cap) {
+  m->ctl_max_layer = cap;
+  m->plan.clear();
+  auto find = [&](int v) { return (int)(std::find(m->exit_ids.begin(), m->exit_ids.end(), v) - m->exit_ids.begin()); };
+  const int ne = (int)m->exit_ids.size();
+  int parity = 0;
+  for (int i = 0; i < m->c.n_layers; ++i) {
+    const bool need_pseudo = find(i + 1) < ne && (i + 1) - m->c.exit_interval < 0 && (i + 1) <= cap;
+    const int k = find(i);
+    const bool is_exit = k < ne && i <= cap;
+    const bool compaction = i >= 2 && m->plan[i - 2].is_exit;
+    parity ^= compaction;
+    m->plan.push_back(PlanRow{need_pseudo, is_exit, is_exit ? k : -1, compaction, parity});
+    if (i >= cap) break;
+  }
+}
+
+bool is_compaction_layer(const deer_model* m, int layer) { return layer < (int)m->plan.size() && m->plan[layer].compaction != 0; }
+// (a layer beyond the plan keeps the last row's map)
+int cmap_parity(const deer_model* m, int layer) { return m->plan[std::min(layer, (int)m->plan.size() - 1)].parity; }
+// a layer with an evaluation writes hidden_states[i]; any other leaves its last residual branch to the next layer
+bool finalized(const PlanRow& r) { return r.need_pseudo || r.is_exit; }
 
 bool use_hl(const deer_model* m, int R) { return !m->c.precision && R > hl_min_rows(); }
 
@@ -1340,6 +1372,29 @@ int llm_layer(deer_model* m, int i, int T, bool use_mask, bool pending_in, bool 
   return DEER_OK;
 }
 
+// One DeterministicDecoder's weights: its offset tables, the buffer they count from and the format of its weight rows.  w() / f() resolve
+// an offset to a device pointer (NULL: the head has no such tensor).
+struct HeadView {
+  const std::vector<LstmW>& lstm;
+  const std::vector<FcW>& fc;
+  size_t wa, ba, wg, bg;
+  const char* base;
+  size_t unit;                       // bytes per offset unit: 1 in the arena, sizeof(float) in a flat f32 parameter buffer
+  int wkind;
+  const void* w(size_t off) const { return off == SIZE_MAX ? nullptr : base + off * unit; }
+  const float* f(size_t off) const { return static_cast<const float*>(w(off)); }
+};
+// from the arena: head 0 = extra_exit (m->lstm / m->fc / m->wa ..), head k = the per-layer head m->lw[k - 1]
+HeadView head_view(const deer_model* m, int head) {
+  if (head == 0) return {m->lstm, m->fc, m->wa, m->ba, m->wg, m->bg, m->arena, 1, m->wkind};
+  const HeadW& h = m->lw[head - 1];
+  return {h.lstm, h.fc, h.wa, h.ba, h.wg, h.bg, m->arena, 1, m->wkind};
+}
+// from a flat f32 parameter buffer (exit-only fine-tuning)
+HeadView head_view(const HeadFlat& F, const float* params) {
+  return {F.lstm, F.fc, F.wa, F.ba, F.wg, F.bg, reinterpret_cast<const char*>(params), sizeof(float), 1};
+}
+
 // One DeterministicDecoder evaluation on hidden_states[layer] (action_head.py:499-611) followed by the exit gate
 // (value_net.py:120-133,277-297).  kind: PSEUDO (prev action from layer i-1, value_net.py:122-125), CHECK (delta <= threshold ->
 // exit + commit LSTM state), COMMIT (static exit_id / committing call)
@@ -1349,10 +1404,8 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
   const int H = m->H, d = m->d, B = m->B;
   // head 0: extra_exit; head k > 0: the k-th per-layer head of layerwise_exit_eval (own weights, own LSTM state, no pre-pass)
   if (head < 0 || head > (int)m->lw.size()) return DEER_ERR_SHAPE;
-  const HeadW* hw = head > 0 ? &m->lw[head - 1] : nullptr;
-  const std::vector<LstmW>& lstm_w = hw ? hw->lstm : m->lstm;
-  const std::vector<FcW>& fc_w = hw ? hw->fc : m->fc;
-  const size_t wa = hw ? hw->wa : m->wa, ba = hw ? hw->ba : m->ba, wg = hw ? hw->wg : m->wg, bg = hw ? hw->bg : m->bg;
+  const HeadW* hw = head > 0 ? &m->lw[head - 1] : nullptr;      // its LSTM state
+  const HeadView hv = head_view(m, head);
   const int* ctl = use_ctl ? m->Wk<int>(m->ctl) : nullptr;
   const size_t rows_cap = std::min(B * c.max_text_len, kMaxRows);
   const bool feats_default = feats == nullptr;
@@ -1376,7 +1429,7 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
   const float* c_prev = m->Wk<float>(hw ? hw->c_state : m->c_state);
   const size_t lst = (size_t)B * H;
   for (int l = 0; l < m->Lh; ++l) {
-    const LstmW& Lw = lstm_w[l];
+    const LstmW& Lw = hv.lstm[l];
     const float* src;
     long bstride;
     int mode, in_dim;
@@ -1384,7 +1437,7 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
     if (l == 0) { src = pooled; bstride = d; mode = DEER_X_RAW; in_dim = d; }
     else {
       src = h_tmp + (l - 1) * lst; bstride = H; in_dim = H;
-      if (c.lstm_layernorm) { mode = DEER_X_LN; lnw = m->A<float>(lstm_w[l - 1].lnw); lnb = m->A<float>(lstm_w[l - 1].lnb); }
+      if (c.lstm_layernorm) { mode = DEER_X_LN; lnw = m->A<float>(hv.lstm[l - 1].lnw); lnb = m->A<float>(hv.lstm[l - 1].lnb); }
       else mode = DEER_X_RAW;
     }
     // control steps (the features are this step's hidden states): the recurrent half comes from deer_begin_step's pre-pass; window mode
@@ -1403,9 +1456,9 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
   const float* src = h_tmp + (m->Lh - 1) * lst;
   int in_dim = H, sstride = H, pro = DEER_PRO_RAW;
   const float* ln[4] = {nullptr, nullptr, nullptr, nullptr};
-  if (c.lstm_layernorm) { pro = DEER_PRO_LN; ln[0] = m->A<float>(lstm_w.back().lnw); ln[1] = m->A<float>(lstm_w.back().lnb); }
+  if (c.lstm_layernorm) { pro = DEER_PRO_LN; ln[0] = m->A<float>(hv.lstm.back().lnw); ln[1] = m->A<float>(hv.lstm.back().lnb); }
   for (int fi = 0; fi < m->n_fc; ++fi) {
-    const FcW& F = fc_w[fi];
+    const FcW& F = hv.fc[fi];
     const int dim = m->fc_dims[fi];
     float* z = m->Wk<float>(m->z_fc[fi]);
     {
@@ -1419,44 +1472,15 @@ int head_eval(deer_model* m, int layer, int T, int kind, int slot, bool force, b
   }
   Bracket b(m, "deer_head_final", 0, 0, st);
   if (env_thr)
-    return deer_head_final_env(src, sstride, in_dim, pro, ln[0], ln[1], ln[2], ln[3], m->A<void>(wa), m->A<float>(ba), m->A<void>(wg), m->A<float>(bg),
+    return deer_head_final_env(src, sstride, in_dim, pro, ln[0], ln[1], ln[2], ln[3], m->A<void>(hv.wa), m->A<float>(hv.ba), m->A<void>(hv.wg), m->A<float>(hv.bg),
                                m->Wk<int>(m->ctl), kind, layer, slot, m->Wk<float>(m->env_exit), force ? 1 : 0, m->thr_type, m->leq, h_tmp, c_tmp,
                                m->Wk<float>(shadow ? m->h_shadow : m->h_state), m->Wk<float>(shadow ? m->c_shadow : m->c_state), m->Lh, H, B,
                                m->Wk<float>(m->action_dbg), kEps, m->wkind, std::max(1, c.multi_step_action), m->Wk<float>(m->act_ext), st);
   const float* thr = m->thr_override ? m->thr_override : m->Wk<float>(m->thresholds);
-  return deer_head_final_multi(src, sstride, in_dim, pro, ln[0], ln[1], ln[2], ln[3], m->A<void>(wa), m->A<float>(ba), m->A<void>(wg), m->A<float>(bg),
+  return deer_head_final_multi(src, sstride, in_dim, pro, ln[0], ln[1], ln[2], ln[3], m->A<void>(hv.wa), m->A<float>(hv.ba), m->A<void>(hv.wg), m->A<float>(hv.bg),
                                no_ctl_final ? nullptr : m->Wk<int>(m->ctl), kind, layer, slot, thr, force ? 1 : 0, m->thr_type, m->leq, h_tmp, c_tmp,
                                m->Wk<float>(shadow ? m->h_shadow : m->h_state), m->Wk<float>(shadow ? m->c_shadow : m->c_state), m->Lh, H, B,
                                m->Wk<float>(m->action_dbg), kEps, m->wkind, std::max(1, c.multi_step_action), m->Wk<float>(m->act_ext), st);
-}
-
-// per layer of the dynamic step: (need_pseudo, is_exit, exit slot) - mosaic_gpt_3b.py:397-443, value_net.py:122-125
-std::vector<PlanRow> dynamic_plan(const deer_model* m) {
-  std::vector<PlanRow> plan;
-  auto find = [&](int v) { return (int)(std::find(m->exit_ids.begin(), m->exit_ids.end(), v) - m->exit_ids.begin()); };
-  const int ne = (int)m->exit_ids.size();
-  for (int i = 0; i < m->c.n_layers; ++i) {
-    const bool need_pseudo = find(i + 1) < ne && (i + 1) - m->c.exit_interval < 0 && (i + 1) <= m->ctl_max_layer;
-    const int k = find(i);
-    const bool is_exit = k < ne && i <= m->ctl_max_layer;
-    plan.push_back(PlanRow{need_pseudo ? 1 : 0, is_exit ? 1 : 0, is_exit ? k : -1});
-    if (i >= m->ctl_max_layer) break;
-  }
-  return plan;
-}
-
-// compaction layers of the dynamic step: two layers after every exit check (its verdict is complete before that layer starts)
-bool is_compaction_layer(const deer_model* m, int layer) {
-  if (layer < 2) return false;
-  const std::vector<PlanRow> plan = dynamic_plan(m);
-  return layer < (int)plan.size() && plan[layer - 2].is_exit != 0;
-}
-
-int cmap_parity(const deer_model* m, int layer) {
-  const std::vector<PlanRow> plan = dynamic_plan(m);
-  int n = 0;
-  for (int l = 2; l <= layer && l < (int)plan.size(); ++l) n += plan[l - 2].is_exit ? 1 : 0;
-  return n & 1;
 }
 
 int embed(deer_model* m, int T, void* st) {
@@ -1467,21 +1491,29 @@ int embed(deer_model* m, int T, void* st) {
   return (m->f16 ? deer_embed_tokens_f16 : deer_embed_tokens)(ids, m->A<void>(m->wte), m->Wk<float>(m->x), m->Wk<int>(m->text_time), T, m->B, m->d, m->c.vocab_size, m->c.media_token_id, st);
 }
 
+// trunk part of layer i of the dynamic step (layer 0 also embeds the tokens)
+int dynamic_main(deer_model* m, int i, int T, bool use_mask, void* st) {
+  if (i == 0) DEER_TRY(embed(m, T, st));
+  return llm_layer(m, i, T, use_mask, i > 0 && !finalized(m->plan[i - 1]), finalized(m->plan[i]), true, st);
+}
+
+// the head evaluations that read hidden_states[i]: the pseudo action and / or the exit check
+int dynamic_heads(deer_model* m, int i, int T, bool use_mask, bool shadow, void* st) {
+  const PlanRow& r = m->plan[i];
+  // rows that are right-padding of an ENV BATCH stay out of the token pool (an independent single-environment run never has
+  // them); with one environment the pool covers all T rows like the reference's (action_head.py:519-520)
+  const bool pm = use_mask && m->B > 1;
+  if (r.need_pseudo) DEER_TRY(head_eval(m, i, T, DEER_KIND_PSEUDO, -1, false, true, false, false, nullptr, pm, st));
+  // the deepest reachable check is forced
+  if (r.is_exit) DEER_TRY(head_eval(m, i, T, DEER_KIND_CHECK, r.slot, i >= m->ctl_max_layer, true, shadow, false, nullptr, pm, st));
+  return DEER_OK;
+}
+
 int llm_dynamic(deer_model* m, int T, bool use_mask, bool shadow, void* st) {
   if (m->c.use_state) return DEER_ERR_SHAPE;            // the reference's dynamic exit raises with use_state (value_net.py:122-129)
-  const std::vector<PlanRow> plan = dynamic_plan(m);
-  bool pending = false;
-  DEER_TRY(embed(m, T, st));
-  for (int i = 0; i < (int)plan.size(); ++i) {
-    const bool fin = plan[i].need_pseudo || plan[i].is_exit;
-    DEER_TRY(llm_layer(m, i, T, use_mask, pending, fin, true, st));
-    pending = !fin;
-    // rows that are right-padding of an ENV BATCH stay out of the token pool (an independent single-environment run never has
-    // them); with one environment the pool covers all T rows like the reference's (action_head.py:519-520)
-    const bool pm = use_mask && m->B > 1;
-    if (plan[i].need_pseudo) DEER_TRY(head_eval(m, i, T, DEER_KIND_PSEUDO, -1, false, true, false, false, nullptr, pm, st));
-    if (plan[i].is_exit)
-      DEER_TRY(head_eval(m, i, T, DEER_KIND_CHECK, plan[i].slot, i >= m->ctl_max_layer, true, shadow, false, nullptr, pm, st));
+  for (int i = 0; i < (int)m->plan.size(); ++i) {
+    DEER_TRY(dynamic_main(m, i, T, use_mask, st));
+    DEER_TRY(dynamic_heads(m, i, T, use_mask, shadow, st));
   }
   return DEER_OK;
 }
@@ -1506,9 +1538,9 @@ int vision(deer_model* m, const VisionWS& ws, int part, bool with_kv, void* st) 
   const int n_head = std::min(kVitHeadLayers, nv - 1);
   const int lo = part == 2 ? n_head : 0, hi = part == 1 ? n_head : nv;
   if (part != 2) DEER_TRY(patch_embed(m, ws, st));
-  DEER_TRY(m->c.precision ? vit_blocks_f32(m, ws, lo, hi, st) : vit_blocks(m, ws, lo, hi, st));
+  DEER_TRY(vit_blocks(m, ws, lo, hi, st));
   if (part != 1) {
-    DEER_TRY(m->c.precision ? perceiver_f32(m, ws, st) : perceiver(m, ws, st));
+    DEER_TRY(perceiver(m, ws, st));
     if (with_kv) DEER_TRY(media_kv(m, st));
   }
   return DEER_OK;
@@ -1550,29 +1582,6 @@ struct ScratchTake {                // carves the scratch into float blocks, eac
     return p;
   }
 };
-
-// One DeterministicDecoder's weights: its offset tables, the buffer they count from and the format of its weight rows.  w() / f() resolve
-// an offset to a device pointer (NULL: the head has no such tensor).
-struct HeadView {
-  const std::vector<LstmW>& lstm;
-  const std::vector<FcW>& fc;
-  size_t wa, ba, wg, bg;
-  const char* base;
-  size_t unit;                       // bytes per offset unit: 1 in the arena, sizeof(float) in a flat f32 parameter buffer
-  int wkind;
-  const void* w(size_t off) const { return off == SIZE_MAX ? nullptr : base + off * unit; }
-  const float* f(size_t off) const { return static_cast<const float*>(w(off)); }
-};
-// from the arena: head 0 = extra_exit (m->lstm / m->fc / m->wa ..), head k = the per-layer head m->lw[k - 1]
-HeadView head_view(const deer_model* m, int head) {
-  if (head == 0) return {m->lstm, m->fc, m->wa, m->ba, m->wg, m->bg, m->arena, 1, m->wkind};
-  const HeadW& h = m->lw[head - 1];
-  return {h.lstm, h.fc, h.wa, h.ba, h.wg, h.bg, m->arena, 1, m->wkind};
-}
-// from a flat f32 parameter buffer (exit-only fine-tuning)
-HeadView head_view(const HeadFlat& F, const float* params) {
-  return {F.lstm, F.fc, F.wa, F.ba, F.wg, F.bg, reinterpret_cast<const char*>(params), sizeof(float), 1};
-}
 
 // Row LayerNorm of the window head; stats (nullable) keeps (mean, rstd) of every row for a backward
 int seq_ln(const float* src, float* dst, const float* w, const float* b, float* stats, int rows, int n, int relu, void* stream) {
@@ -1675,7 +1684,8 @@ int deer_model_create(const deer_config* cfg, deer_model** out) {
   // default controller: exits every exit_interval layers + the last layer (flamingo_mpt.py:239-250,268-270)
   for (int i = c.exit_interval - 1; i < c.n_layers - 1; i += c.exit_interval) m->exit_ids.push_back(i);
   m->exit_ids.push_back(c.n_layers - 1);
-  m->ctl_max_layer = m->cfg_max_layer = m->exit_ids.back();
+  m->cfg_max_layer = m->exit_ids.back();
+  set_max_layer(m, m->cfg_max_layer);
   if (const char* e = getenv("DEER_COMPACT")) m->compact = e[0] != '0';
   if (const char* e = getenv("DEER_HEAD_PRE")) m->head_pre = e[0] != '0';
   *out = m;
@@ -1819,7 +1829,8 @@ int deer_model_configure_exit(deer_model* m, const int* exit_ids, int n_exit, in
   for (int i = 0; i < n_exit; ++i) ok = ok || exit_ids[i] == cm;
   if (!ok) return DEER_ERR_SHAPE;
   m->exit_ids.assign(exit_ids, exit_ids + n_exit);
-  m->ctl_max_layer = m->cfg_max_layer = cm;
+  m->cfg_max_layer = cm;
+  set_max_layer(m, cm);
   m->thr_type = thr_type;
   m->leq = leq ? 1 : 0;
   m->env_exit_on = false;                                                     // caps were validated against the old exits
@@ -1838,7 +1849,7 @@ static int env_exit_set(deer_model* m, const float* rows, int rows_on_device, co
   }
   DEER_TRY(deer_env_exit_write(m->Wk<float>(m->env_exit), rows, rows_on_device, eff, n_envs, stream));
   m->env_exit_on = true;
-  m->ctl_max_layer = cmax;
+  set_max_layer(m, cmax);
   return DEER_OK;
 }
 
@@ -1853,7 +1864,7 @@ int deer_model_set_env_exit_device(deer_model* m, const float* rows, const int* 
 int deer_model_clear_env_exit(deer_model* m) {
   if (m == nullptr) return DEER_ERR_SHAPE;
   m->env_exit_on = false;
-  m->ctl_max_layer = m->cfg_max_layer;
+  set_max_layer(m, m->cfg_max_layer);
   return DEER_OK;
 }
 
@@ -1868,7 +1879,7 @@ int deer_model_real_num_exit(const deer_model* m) {
 int deer_model_n_chains(const deer_model* m) { return (int)m->chains.size(); }
 
 int deer_dynamic_plan(const deer_model* m, int* need_pseudo, int* is_exit, int* slot, int cap) {
-  const std::vector<PlanRow> plan = dynamic_plan(m);
+  const std::vector<PlanRow>& plan = m->plan;
   for (int i = 0; i < (int)plan.size() && i < cap; ++i) {
     if (need_pseudo) need_pseudo[i] = plan[i].need_pseudo;
     if (is_exit) is_exit[i] = plan[i].is_exit;
@@ -1922,6 +1933,20 @@ int deer_head_eval(deer_model* m, int layer, int T, int kind, int slot, int forc
                    int use_mask, void* stream) {
   if (m->ws == nullptr || layer < 0 || layer >= m->c.n_layers || T <= 0 || kind < 0 || kind > 2) return DEER_ERR_SHAPE;
   return head_eval(m, layer, T, kind, slot, force != 0, use_ctl != 0, shadow != 0, no_ctl_final != 0, feats, use_mask != 0, stream);
+}
+
+// One graph piece of the segmented schedules: the same functions deer_step_enqueue runs, cut where the host may stop submitting
+int deer_step_piece(deer_model* m, int piece, int index, int T, int use_mask, void* stream) {
+  if (m->ws == nullptr || T <= 0 || T > m->c.max_text_len || m->B * T > kMaxRows || index < 0) return DEER_ERR_SHAPE;
+  if (piece == DEER_PIECE_STATIC) {
+    if (index >= m->c.n_layers) return DEER_ERR_SHAPE;
+    DEER_TRY(media_kv(m, stream));
+    return llm_static(m, T, use_mask != 0, index, stream);
+  }
+  if ((piece != DEER_PIECE_MAIN && piece != DEER_PIECE_HEADS) || m->c.use_state || index >= (int)m->plan.size()) return DEER_ERR_SHAPE;
+  if (piece == DEER_PIECE_HEADS) return finalized(m->plan[index]) ? dynamic_heads(m, index, T, use_mask != 0, false, stream) : DEER_ERR_SHAPE;
+  if (index == 0) DEER_TRY(media_kv(m, stream));
+  return dynamic_main(m, index, T, use_mask != 0, stream);
 }
 
 // layerwise_exit_eval (flamingo_mpt.py:450-457): the action of exit layer `layer` from that layer's OWN head (head = 1 + its index in the
@@ -2379,12 +2404,7 @@ long deer_model_scratch_bytes(const deer_model* m) { return (long)(m->seq_bytes 
 int deer_step_enqueue(deer_model* m, int T, int use_mask, int exit_id, int shadow, const int* step_info, void* stream) {
   if (m->ws == nullptr || T <= 0 || T > m->c.max_text_len || m->B * T > kMaxRows || exit_id >= m->c.n_layers) return DEER_ERR_SHAPE;
   DEER_TRY(deer_begin_step(m, step_info, stream));
-  if (m->c.sep_resampler) {                             // one chain per camera (own Perceiver weights), same stream
-    for (const VisionWS& cw : m->chains) DEER_TRY(vision(m, cw, 0, false, stream));
-    DEER_TRY(media_kv(m, stream));
-  } else {
-    DEER_TRY(vision(m, m->vws, 0, true, stream));
-  }
+  DEER_TRY(deer_vision(m, -1, 0, 1, stream));
   return exit_id < 0 ? llm_dynamic(m, T, use_mask != 0, shadow != 0, stream) : llm_static(m, T, use_mask != 0, exit_id, stream);
 }
 
@@ -2393,7 +2413,7 @@ int deer_vit_l14_encode(deer_model* m, const void* images_bf16, int n_images, fl
   if (m->ws == nullptr || images_bf16 == nullptr || n_images != m->N) return DEER_ERR_SHAPE;
   m->img_override = images_bf16;
   int rc = patch_embed(m, m->vws, stream);
-  if (rc == DEER_OK) rc = m->c.precision ? vit_blocks_f32(m, m->vws, 0, m->c.vit_layers, stream) : vit_blocks(m, m->vws, 0, m->c.vit_layers, stream);
+  if (rc == DEER_OK) rc = vit_blocks(m, m->vws, 0, m->c.vit_layers, stream);
   m->img_override = nullptr;
   if (rc != DEER_OK) return rc;
   if (tokens_out != nullptr) {   // patch tokens x[:, 1:] of every image, without ln_post (flamingo_mpt.py:580)
@@ -2412,9 +2432,9 @@ int deer_perceiver_resample(deer_model* m, const float* tokens, int n_images, vo
   int rc = DEER_OK;
   if (m->c.sep_resampler) {                             // frames camera-major: one pass per camera with its own weight set
     for (const VisionWS& cw : m->chains)
-      if (rc == DEER_OK) rc = m->c.precision ? perceiver_f32(m, cw, stream) : perceiver(m, cw, stream);
+      if (rc == DEER_OK) rc = perceiver(m, cw, stream);
   } else {
-    rc = m->c.precision ? perceiver_f32(m, m->vws, stream) : perceiver(m, m->vws, stream);
+    rc = perceiver(m, m->vws, stream);
   }
   m->tokens_override = nullptr;
   if (rc != DEER_OK) return rc;

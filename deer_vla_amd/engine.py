@@ -294,9 +294,6 @@ class DeerEngine:
         abi.check(self.lib.deer_vision(self._h, chain, {"all": 0, "head": 1, "tail": 2}[part], 1 if kv_all else 0, _cur_stream()),
                   "deer_vision")
 
-    def _enqueue_media_kv(self):
-        abi.check(self.lib.deer_media_kv(self._h, _cur_stream()), "deer_media_kv")
-
     def enqueue_embed(self, T):
         abi.check(self.lib.deer_llm_embed(self._h, T, _cur_stream()), "deer_llm_embed")
 
@@ -513,32 +510,10 @@ class DeerEngine:
             self._plan_key = key
         return self._plan
 
-    def enqueue_dynamic_main(self, T, use_mask, i):
-        """Trunk part of layer i of the dynamic step (layer 0 also embeds the tokens)."""
-        plan = self.dynamic_plan()
-        _, need_pseudo, is_exit, _ = plan[i]
-        if i == 0:
-            self.enqueue_embed(T)
-        prev_open = i > 0 and not (plan[i - 1][1] or plan[i - 1][2])          # previous layer not finalized -> residual pending
-        self.enqueue_llm_layer(i, T, prev_open, use_mask, finalize=(need_pseudo or is_exit))
-
-    def enqueue_dynamic_heads(self, T, i, shadow: bool = False, use_mask: bool = False):
-        """Head evaluations that read hidden_states[i]: the layer-0 pseudo action and/or the exit check."""
-        _, need_pseudo, is_exit, slot = self.dynamic_plan()[i]
-        pm = use_mask and self.B > 1          # rows of an env batch that are right-padding stay out of the token pool
-        if need_pseudo:
-            self.enqueue_head(i, T, abi.KIND_PSEUDO, use_mask=pm)
-        if is_exit:
-            self.enqueue_head(i, T, abi.KIND_CHECK, slot=slot, force=(i >= self.ctl_max_layer), shadow=shadow, use_mask=pm)
-
-    def enqueue_llm_static(self, T, use_mask, exit_id):
-        """exit_id given (flamingo_mpt.py:402-411,446-461): run layers 0..exit_id, committing head call."""
-        if getattr(self.cfg, "use_state", False):
-            abi.check(self.lib.deer_head_state(self._h, _cur_stream()), "deer_head_state")
-        self.enqueue_embed(T)
-        for i in range(exit_id + 1):
-            self.enqueue_llm_layer(i, T, None, use_mask, finalize=True, ctl=False)
-        self.enqueue_head(exit_id, T, abi.KIND_COMMIT, use_ctl=False, use_mask=use_mask and self.B > 1)
+    def _enqueue_piece(self, piece: int, index: int, T, use_mask):
+        """One graph piece of the segmented schedules (include/deer_model.h deer_step_piece): PIECE_MAIN / PIECE_HEADS of layer ``index`` of
+        the dynamic plan, or PIECE_STATIC up to exit ``index``.  What a piece holds is the spine's decision."""
+        abi.check(self.lib.deer_step_piece(self._h, piece, index, T, 1 if use_mask else 0, _cur_stream()), "deer_step_piece")
 
     def _drain_side_streams(self):
         # an unconditional stream-wait (event record + wait: ~6 us of host time, nothing on the device when the stream is idle);
@@ -789,8 +764,7 @@ class DeerEngine:
             self._vision_chain_graphs()
             g = torch.cuda.CUDAGraph()
             with _capture(g):
-                self._enqueue_media_kv()
-                self.enqueue_llm_static(T, use_mask, exit_id)
+                self._enqueue_piece(abi.PIECE_STATIC, exit_id, T, use_mask)
             self._graphs[key] = g
         else:
             tm = self._time_stages
@@ -866,14 +840,12 @@ class DeerEngine:
             for i, need_pseudo, is_exit, _ in plan:
                 g = torch.cuda.CUDAGraph()
                 with _capture(g):
-                    if i == 0:
-                        self._enqueue_media_kv()
-                    self.enqueue_dynamic_main(T, use_mask, i)
+                    self._enqueue_piece(abi.PIECE_MAIN, i, T, use_mask)
                 P["main"].append(g)
                 if need_pseudo or is_exit:
                     gh = torch.cuda.CUDAGraph()
                     with _capture(gh):
-                        self.enqueue_dynamic_heads(T, i, use_mask=use_mask)
+                        self._enqueue_piece(abi.PIECE_HEADS, i, T, use_mask)
                     P["head"][i] = gh
             P["native"] = self._make_step_plan(P, plan)
             self._graphs[key] = P
@@ -916,19 +888,20 @@ class DeerEngine:
             self._siblings[(n_envs, index)] = e
         return e
 
-    def window_hidden_states(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8) -> torch.Tensor:
-        """hidden_states of EVERY layer for each frame pair of calibration windows (the ``hidden_states`` the reference's window-mode
-        forward hands to ``ActionValueNet(mode='generate')``: flamingo_mpt.py:463-517 on (bs*W) batch rows, value_net.py:375-386).
-        rgb_seq / grip_seq: (F, 3, S, S) frames; ids (F, T) or (1, T) (one instruction for all frames); returns (F, n_layers, T, d)
-        fp32 on the device.  The frames are BATCH ROWS here too: groups of ``group`` frames run through the env-batch sibling
-        engine (ViT at M = 514*group rows, trunk at group*T rows), static full depth, every layer's output kept."""
+    def _window_group(self, F: int, T: int, group: int) -> int:
+        """frames per group of the window pass"""
+        return max(1, min(group, self.MAX_ROWS // T, F, abi.MAX_ENVS))
+
+    def _window_pass(self, rgb_seq, grip_seq, ids, mask, group: int, read_out):
+        """The grouped static full-depth pass of window mode: the F frames are BATCH ROWS, groups of G = ``_window_group`` of them run
+        through the env-batch sibling engine (ViT at M = 514*G rows, trunk at G*T rows), every layer's output kept.
+        ``read_out(sibling, f0, n_real, G, T)`` runs behind each group's step, on that group's stream: frames f0 .. f0 + n_real - 1 are the
+        first n_real of the sibling's G batch rows (the last group is padded with its last frame)."""
         F = rgb_seq.shape[0]
         ids = ids.reshape(-1, ids.shape[-1])
         T = ids.shape[1]
-        G = max(1, min(group, self.MAX_ROWS // T, F, abi.MAX_ENVS))
+        G = self._window_group(F, T, group)
         last = self.cfg.n_layers - 1
-        L, d = self.cfg.n_layers, self.cfg.d_model
-        out = torch.empty(F, L, T, d, device=self.dev)
         # more than one group: two sibling engines alternate, each on its own stream - one group's MFMA-bound vision tower runs
         # beside the other's HBM-bound trunk (two groups of 6: 12.0 instead of 14.8 ms, tools/overlap_two_batches.py)
         n_groups = (F + G - 1) // G
@@ -951,10 +924,23 @@ class DeerEngine:
                 T_, use_mask = w.load_inputs(rgb_seq[idx], grip_seq[idx], ids_g.contiguous(), mask_g)
                 w.hold_dev.zero_()
                 w._enqueue_step(T_, use_mask, last)               # static full depth: every layer's output is kept
-                n = min(G, F - f0)
-                out[f0:f0 + n].copy_(w.hidden[:, :G * T].view(L, G, T, d).permute(1, 0, 2, 3)[:n])
+                read_out(w, f0, min(G, F - f0), G, T_)
         if n_groups > 1:
             cur.wait_stream(self._side_stream)
+
+    def _copy_window_hidden(self, out, w, f0, n, G, T):
+        """out[f0:f0 + n] of (F, n_layers, T, d) <- the hidden states of the first n batch rows of sibling ``w``'s step"""
+        L, d = self.cfg.n_layers, self.cfg.d_model
+        out[f0:f0 + n].copy_(w.hidden[:, :G * T].view(L, G, T, d).permute(1, 0, 2, 3)[:n])
+
+    def window_hidden_states(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8) -> torch.Tensor:
+        """hidden_states of EVERY layer for each frame pair of calibration windows (the ``hidden_states`` the reference's window-mode
+        forward hands to ``ActionValueNet(mode='generate')``: flamingo_mpt.py:463-517 on (bs*W) batch rows, value_net.py:375-386).
+        rgb_seq / grip_seq: (F, 3, S, S) frames; ids (F, T) or (1, T) (one instruction for all frames); returns (F, n_layers, T, d)
+        fp32 on the device.  The frames are BATCH ROWS here too: groups of ``group`` frames run through the env-batch sibling
+        engine (ViT at M = 514*group rows, trunk at group*T rows), static full depth, every layer's output kept."""
+        out = torch.empty(rgb_seq.shape[0], self.cfg.n_layers, ids.shape[-1], self.cfg.d_model, device=self.dev)
+        self._window_pass(rgb_seq, grip_seq, ids, mask, group, lambda w, f0, n, G, T: self._copy_window_hidden(out, w, f0, n, G, T))
         return out
 
     def window_exit_features(self, rgb_seq: torch.Tensor, grip_seq: torch.Tensor, ids: torch.Tensor, mask=None, group: int = 8) -> torch.Tensor:
@@ -963,37 +949,16 @@ class DeerEngine:
         NL = 1 + n_exit - ``n_layers * T / NL`` times less than the (F, n_layers, T, d) hidden states.  The same grouped static full-depth pass
         (two alternating siblings on two streams); each group ends in one ``deer_pool_exit_layers`` launch instead of the permuted copy."""
         F = rgb_seq.shape[0]
-        ids = ids.reshape(-1, ids.shape[-1])
-        T = ids.shape[1]
-        G = max(1, min(group, self.MAX_ROWS // T, F, abi.MAX_ENVS))
-        last = self.cfg.n_layers - 1
-        NL, d = len(self.exit_ids) + 1, self.cfg.d_model
+        G = self._window_group(F, ids.shape[-1], group)
         n_groups = (F + G - 1) // G
-        out = torch.empty(n_groups * G, NL, d, device=self.dev)    # whole groups: the padded frames of the last one are cut off below
-        ws = [self.sibling(G)] + ([self.sibling(G, 1)] if n_groups > 1 else [])
-        cur = torch.cuda.current_stream()
-        sts = [cur] + ([self._side_stream] if n_groups > 1 else [])
-        for w in ws:
-            w._drain_side_streams()
+        out = torch.empty(n_groups * G, len(self.exit_ids) + 1, self.cfg.d_model, device=self.dev)    # whole groups: the padded frames of the last one are cut off below
+        for w in [self.sibling(G)] + ([self.sibling(G, 1)] if n_groups > 1 else []):
             if list(w.exit_ids) != list(self.exit_ids):           # the pooled layers are the sibling model's configured exits
                 w.configure_exit(self.exit_ids, self.exit_ids[-1] + 1)
-        if n_groups > 1:
-            self._side_stream.wait_stream(cur)                    # inputs produced on the caller's stream
-        for gi, f0 in enumerate(range(0, F, G)):
-            w, st = ws[gi % len(ws)], sts[gi % len(ws)]
-            with torch.cuda.stream(st):
-                idx = [min(f0 + i, F - 1) for i in range(G)]      # the last group is padded with its last frame
-                ids_g = ids[idx] if ids.shape[0] == F else ids.expand(G, T)
-                mask_g = None
-                if mask is not None:
-                    m2 = mask.reshape(-1, T)
-                    mask_g = m2[idx] if m2.shape[0] == F else m2.expand(G, T)
-                T_, use_mask = w.load_inputs(rgb_seq[idx], grip_seq[idx], ids_g.contiguous(), mask_g)
-                w.hold_dev.zero_()
-                w._enqueue_step(T_, use_mask, last)               # static full depth: every layer's output is kept
-                abi.check(w.lib.deer_pool_exit_layers(w._h, G, T_, abi.ptr(out[f0:f0 + G]), _cur_stream()), "deer_pool_exit_layers")
-        if n_groups > 1:
-            cur.wait_stream(self._side_stream)
+
+        def read_out(w, f0, n, G, T):
+            abi.check(w.lib.deer_pool_exit_layers(w._h, G, T, abi.ptr(out[f0:f0 + G]), _cur_stream()), "deer_pool_exit_layers")
+        self._window_pass(rgb_seq, grip_seq, ids, mask, group, read_out)
         return out[:F]
 
     def calibrate_values(self, feats: torch.Tensor, rand_layers, threshold_type: str = "L2", return_actions: bool = False):
@@ -1083,40 +1048,16 @@ class DeerEngine:
         feature (action_head.py:519-520, all T rows) of every exit layer ``cfg.exit_ids()``, (F, NE, d) fp32 on the device - each group ends
         in one ``deer_pool_window_layers`` launch.  hidden=True also returns the (F, n_layers, T, d) hidden states (``output.hidden_states``
         of the reference)."""
-        F = rgb_seq.shape[0]
-        ids = ids.reshape(-1, ids.shape[-1])
-        T = ids.shape[1]
-        G = max(1, min(group, self.MAX_ROWS // T, F, abi.MAX_ENVS))
-        last = self.cfg.n_layers - 1
-        L, d, NE = self.cfg.n_layers, self.cfg.d_model, len(self.cfg.exit_ids())
-        n_groups = (F + G - 1) // G
-        out = torch.empty(n_groups * G, NE, d, device=self.dev)    # whole groups: the padded frames of the last one are cut off below
-        hid = torch.empty(F, L, T, d, device=self.dev) if hidden else None
-        ws = [self.sibling(G)] + ([self.sibling(G, 1)] if n_groups > 1 else [])
-        cur = torch.cuda.current_stream()
-        sts = [cur] + ([self._side_stream] if n_groups > 1 else [])
-        for w in ws:
-            w._drain_side_streams()
-        if n_groups > 1:
-            self._side_stream.wait_stream(cur)                    # inputs produced on the caller's stream
-        for gi, f0 in enumerate(range(0, F, G)):
-            w, st = ws[gi % len(ws)], sts[gi % len(ws)]
-            with torch.cuda.stream(st):
-                idx = [min(f0 + i, F - 1) for i in range(G)]      # the last group is padded with its last frame
-                ids_g = ids[idx] if ids.shape[0] == F else ids.expand(G, T)
-                mask_g = None
-                if mask is not None:
-                    m2 = mask.reshape(-1, T)
-                    mask_g = m2[idx] if m2.shape[0] == F else m2.expand(G, T)
-                T_, use_mask = w.load_inputs(rgb_seq[idx], grip_seq[idx], ids_g.contiguous(), mask_g)
-                w.hold_dev.zero_()
-                w._enqueue_step(T_, use_mask, last)               # static full depth: every layer's output is kept
-                abi.check(w.lib.deer_pool_window_layers(w._h, G, T_, abi.ptr(out[f0:f0 + G]), _cur_stream()), "deer_pool_window_layers")
-                if hidden:
-                    n = min(G, F - f0)
-                    hid[f0:f0 + n].copy_(w.hidden[:, :G * T].view(L, G, T, d).permute(1, 0, 2, 3)[:n])
-        if n_groups > 1:
-            cur.wait_stream(self._side_stream)
+        F, T = rgb_seq.shape[0], ids.shape[-1]
+        G = self._window_group(F, T, group)
+        out = torch.empty((F + G - 1) // G * G, len(self.cfg.exit_ids()), self.cfg.d_model, device=self.dev)    # whole groups: the padded frames of the last one are cut off below
+        hid = torch.empty(F, self.cfg.n_layers, T, self.cfg.d_model, device=self.dev) if hidden else None
+
+        def read_out(w, f0, n, G, T):
+            abi.check(w.lib.deer_pool_window_layers(w._h, G, T, abi.ptr(out[f0:f0 + G]), _cur_stream()), "deer_pool_window_layers")
+            if hidden:
+                self._copy_window_hidden(hid, w, f0, n, G, T)
+        self._window_pass(rgb_seq, grip_seq, ids, mask, group, read_out)
         return (out[:F], hid) if hidden else out[:F]
 
     def exit_outputs(self, feats, rand_layers, two_layers, state=None) -> torch.Tensor:

@@ -149,6 +149,17 @@ int deer_llm_layer(deer_model* m, int layer, int T, int use_mask, int pending_in
 /* one DeterministicDecoder evaluation + exit gate.  feats: NULL = hidden[layer]; kind DEER_KIND_*; slot = exit index */
 int deer_head_eval(deer_model* m, int layer, int T, int kind, int slot, int force, int use_ctl, int shadow, int no_ctl_final,
                    const float* feats, int use_mask, void* stream);
+/* One graph piece of a control step whose vision chains ran as deer_vision(chain, part, 0): what deer_step_enqueue runs behind the tower,
+ * cut where the host may stop submitting (engine.py captures one HIP graph per piece; deer_dynamic_plan says which pieces exist).
+ *   DEER_PIECE_MAIN, i          trunk layer i of the dynamic plan with the plan's pending / finalize flags; i = 0 first projects the media
+ *                               K|V and embeds the tokens
+ *   DEER_PIECE_HEADS, i         the pseudo-action evaluation and / or the exit check that read hidden[i] (never a shadow step's);
+ *                               DEER_ERR_SHAPE when the plan has neither for layer i
+ *   DEER_PIECE_STATIC, exit_id  media K|V, [robot-state embedding,] token embedding, layers 0 .. exit_id, the committing head evaluation
+ * DEER_ERR_SHAPE (nothing enqueued): no workspace, T or n_envs * T out of range, index outside the plan (MAIN / HEADS) or the layers
+ * (STATIC), MAIN / HEADS on a use_state model (no dynamic exit there). */
+enum { DEER_PIECE_MAIN = 0, DEER_PIECE_HEADS = 1, DEER_PIECE_STATIC = 2 };
+int deer_step_piece(deer_model* m, int piece, int index, int T, int use_mask, void* stream);
 /* layerwise_exit_eval: head index (1-based, the reference's registration order) of an exit layer or -1; one evaluation of that head on
  * hidden[layer] from ITS LSTM state (workspace "lw_state": [head][h, c][L][n_envs][H]); outputs in "action_dbg", new state in h_tmp / c_tmp */
 int deer_model_layerwise_head(const deer_model* m, int layer);
